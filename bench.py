@@ -97,7 +97,13 @@ def parse():
                    "experiment switches, e.g. 'LM_WFA_R16=0|LM_TWO_LANES=0 LM_WFA_R16=0' (variants separated by |, one warm-up + "
                    "--ab-steps steps each; reported under 'ab', not part of the metric)")
     p.add_argument("--ab-steps", type=int, default=2)
-    return p.parse_args()
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write the HSP rows of the last timed step as DIR/<column>.npy (float64, "
+                        "at most 64 MB in all: a fixed seeded sample of the rows above that) to compare two builds")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
 
 
 WORKLOADS = {
@@ -360,6 +366,28 @@ def maybe_spawn(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.abspath(__file__)] + sys.argv[1:]
     raise SystemExit(subprocess.call(cmd, env=env))
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(rows, out_dir, skip=(), limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every column of the row records `rows` but those named in `skip` as DIR/<column>.npy in float64
+    (the integer columns are below 2^53: exact), and DIR/row.npy, the numbers of the rows written.  When all rows would
+    exceed `limit` bytes, a sample of the rows drawn with a fixed seed is written, in row order: two builds that compute
+    the same rows write the same files."""
+    import numpy as np
+    names = [n for n in rows.dtype.names if n not in skip]
+    nfiles = len(names) + 1
+    keep = max(0, (limit - 256 * nfiles) // (8 * nfiles))  # (an .npy header is at most 256 bytes here)
+    idx = np.arange(len(rows))
+    if len(rows) > keep:
+        idx = np.sort(np.random.default_rng(0).choice(len(rows), keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "row.npy"), idx.astype(np.float64))
+    for n in names:
+        np.save(os.path.join(out_dir, n + ".npy"), rows[n][idx].astype(np.float64))
+    return dict(dir=out_dir, rows=int(len(rows)), rows_written=int(len(idx)), columns=names)
 
 
 def draw_query(np, synth, rng, seq, wl, as_read=False):
@@ -724,6 +752,13 @@ def main():
         dt = float(tt.item())
     gi.profile_mark(2)
     prof = gi.profile_get()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the timed path returned in its last step (rank 0: the merged rows of an N-GPU run); the pointer columns hold
+        # process-local addresses of the names and strings, not values
+        dumped = dump_outputs(rows_np, args.dump_outputs, skip=merge.PTR_FIELDS)
+        log("[rank 0] outputs of the last timed step: %d of %d rows in %s" % (dumped["rows_written"], dumped["rows"],
+                                                                             args.dump_outputs))
     # the printer (search.go:437-533: one writer goroutine) on the rows of the last timed step: lm_format_rows (host threads, one
     # buffer) + one write to /dev/null - what the reference's queries/s includes and the timed region above does not
     host_e2e = None
@@ -1010,6 +1045,8 @@ def main():
             "ab": ab,
             "source_hash": source_hash(),
         }
+        if dumped:
+            result["dump_outputs"] = dumped
     # The FULL-SIZE index against the oracle (the sample leg below only meets a second, small index): the search is independent
     # per genome (lib-index-search.go:1537-1556,1743-1747), so (1) the sample queries searched on the full index with the genome
     # whitelist = the sample genomes must give the oracle's rows on the sample index (compared after the CPU leg), and (2) the

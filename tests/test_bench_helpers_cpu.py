@@ -210,3 +210,37 @@ def test_source_hash_ignores_comments_and_whitespace_but_not_code():
     assert bench._code_only(a) == bench._code_only(b) != bench._code_only(c)
     assert '"// not a comment"' in bench._code_only(a)
     assert len(bench.source_hash()) == 16 and bench.source_hash() != bench.source_hash_raw()
+
+
+def test_dump_outputs_writes_float_columns_and_a_fixed_sample_within_the_limit(tmp_path):
+    """--dump-outputs: one float64 .npy per value column of the lm_hsp rows (no pointer column), all rows when they fit,
+    else the same seeded sample on every run, never more bytes than the limit"""
+    import bench
+    from lexicmap_amd.merge import PTR_FIELDS, ROW_DTYPE
+    rows = np.zeros(5000, dtype=ROW_DTYPE)
+    rows["query"] = np.arange(5000) // 7
+    rows["batch_genome"] = (np.arange(5000, dtype=np.uint64) % 300) << np.uint64(17)
+    rows["pident"] = np.linspace(50, 100, 5000)
+    rows["cigar"] = 12345  # an address: not a value
+    cols = [n for n in ROW_DTYPE.names if n not in PTR_FIELDS]
+
+    d = tmp_path / "all"
+    info = bench.dump_outputs(rows, str(d), skip=PTR_FIELDS)
+    assert info["rows"] == info["rows_written"] == 5000 and info["columns"] == cols
+    assert sorted(os.listdir(d)) == sorted([c + ".npy" for c in cols] + ["row.npy"])
+    for c in cols:
+        a = np.load(d / (c + ".npy"))
+        assert a.dtype == np.float64 and np.array_equal(a, rows[c].astype(np.float64))
+
+    limit = 200_000
+    runs = []
+    for k in range(2):
+        d = tmp_path / ("sample%d" % k)
+        info = bench.dump_outputs(rows, str(d), skip=PTR_FIELDS, limit=limit)
+        assert 0 < info["rows_written"] < 5000
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= limit
+        idx = np.load(d / "row.npy").astype(np.int64)
+        assert np.all(np.diff(idx) > 0)
+        assert np.array_equal(np.load(d / "batch_genome.npy"), rows["batch_genome"][idx].astype(np.float64))
+        runs.append(idx)
+    assert np.array_equal(runs[0], runs[1])
