@@ -148,15 +148,16 @@ def test_clear_and_chain1_match_oracle(n, qspan, tspan, seed):
     for i in range(n_o):
         assert (da[i].qbegin, da[i].tbegin, da[i].len, da[i].qrc, da[i].trc) == \
                (oa[i].qbegin, oa[i].tbegin, oa[i].len, oa[i].qrc, oa[i].trc)
-    lut = gap_lut()
-    for (max_gap, max_dist, top) in ((50.0, 1000.0, 0), (50.0, 1000.0, 1), (20.0, 300.0, 2)):
+    for (max_gap, max_dist, top) in ((50.0, 1000.0, 0), (50.0, 1000.0, 1), (20.0, 300.0, 2), (5.0, 100.0, 0),
+                                     (200.0, 10000.0, 0)):
+        lut = gap_lut(max(64, int(np.ceil(max_gap)) + 2))  # (lm_fill_gap_lut: ceil(max_gap) + 2 entries)
         min_score = L.lmo_seed_weight(17.0)
         coff, cidx, nch = C.POINTER(C.c_int)(), C.POINTER(C.c_int)(), C.c_int()
         so = L.lmo_chainer(oa, n_o, max_gap, min_score, max_dist, top, C.byref(coff), C.byref(cidx), C.byref(nch))
         doff = (C.c_int32 * (n_o + 4))()
         didx = (C.c_int32 * (2 * n_o + 6))()
         dn = C.c_int()
-        sd = Hh.ha_chain1(da, n_o, max_gap, min_score, max_dist, top, lut, 64, doff, didx, C.byref(dn))
+        sd = Hh.ha_chain1(da, n_o, max_gap, min_score, max_dist, top, lut, len(lut), doff, didx, C.byref(dn))
         assert np.float32(sd).tobytes() == np.float32(so).tobytes()
         assert dn.value == nch.value
         assert [doff[i] for i in range(dn.value + 1)] == [coff[i] for i in range(nch.value + 1)]

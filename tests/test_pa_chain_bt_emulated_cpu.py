@@ -76,6 +76,16 @@ def test_several_chains_and_the_regions_between_them(n, pieces, seed):
     assert check(broken(rng, n, pieces), pident=80.0, min_score=60)[0] == 0
 
 
+@pytest.mark.parametrize("band,max_gap", [(20, 5), (140, 20), (400, 20), (400, 100), (1000, 100)])
+def test_wide_and_narrow_bands(band, max_gap):
+    """--align-band / --align-max-gap away from 100 / 20: band_count = band / 2 candidates (70, 200, 500 reach past the
+    64 registers and the LDS ring of the DP)"""
+    rng = random.Random(band + max_gap)
+    for anchors in (colinear(rng, 1500), broken(rng, 1500, 6)):
+        bad, nch = check(anchors, max_gap=max_gap, band_base=band, band_count=band // 2)
+        assert bad == 0 and nch >= 1
+
+
 def test_degenerate_inputs():
     rng = random.Random(21)
     assert check([(10, 10, 20), (10, 50, 20)])[0] == 0

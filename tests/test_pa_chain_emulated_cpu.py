@@ -52,7 +52,12 @@ def colinear(rng, n, step=(5, 60), noise=0.2, jump=0.02):
 
 @pytest.mark.parametrize("n,seed,kw", [(2, 1, {}), (3, 2, {}), (64, 3, {}), (65, 4, {}), (130, 5, {}), (700, 6, {}), (3000, 7, {}),
                                        (900, 8, dict(band_base=2000, band_count=200)),   # the band reaches behind the ring
-                                       (500, 9, dict(band_base=0, band_count=3)), (400, 10, dict(max_gap=0))])
+                                       (500, 9, dict(band_base=0, band_count=3)), (400, 10, dict(max_gap=0)),
+                                       # --align-band 140 / 400 / 1000 (count 70 / 200 / 500), --align-max-gap 100
+                                       (700, 11, dict(band_base=140, band_count=70)),
+                                       (900, 12, dict(band_base=400, band_count=200)),
+                                       (900, 13, dict(band_base=400, band_count=200, max_gap=100)),
+                                       (1200, 14, dict(band_base=1000, band_count=500, max_gap=100))])
 def test_ring_dp_equals_lm_run_chain2(n, seed, kw):
     rng = random.Random(seed)
     for rep in range(3):
