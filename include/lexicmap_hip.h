@@ -208,10 +208,15 @@ typedef struct lm_stage lm_stage; /* host arrays of a stage-level call, released
  * idx (may be NULL) re-attaches genome_id / seq_id: every shard holds the names of all genomes.  cigar/qseq/sseq/align
  * are process-local and come back NULL.  Free with lm_result_free. */
 lm_status lm_merge_sharded(lm_index *idx, const lm_hsp *const *rows, const size_t *nrows, int nshards, lm_result **out);
+/* The same merge with the printer's flags: flags = 0 is lm_merge_sharded.  flags = LM_ROW_ALL (-a/--all): the cigar / qseq /
+ * sseq / align pointers of the input rows are live in THIS process (e.g. the rows lm_gather_rows_ex returns with LM_ROW_ALL)
+ * and every string is copied into storage the result owns, following its row into the merged order; a NULL string stays NULL,
+ * "" stays "".  Other bits: LM_ERR_ARG. */
+lm_status lm_merge_sharded_ex(lm_index *idx, const lm_hsp *const *rows, const size_t *nrows, int nshards, int flags, lm_result **out);
 
 /* The ONE collective of the sharded search (north_star: "per-shard hit lists merged with a single RCCL all-gatherv over
  * xGMI"), behind the C-ABI so that the Go host needs nothing else: a gatherv of lm_hsp records to the merging rank - an
- * all-gather of the row counts (8 bytes per rank), then one group of point-to-point transfers into the root ((N-1) payloads
+ * all-gather of the counts (24 bytes per rank), then one group of point-to-point transfers into the root ((N-1) payloads
  * over the root's xGMI links; the ranks that do not merge receive nothing).  What the gathered rows are merged into:
  * lm_merge_sharded above (lib-index-search.go:2919-2921, merge-search-results.go:142-194).
  *   lm_comm_unique_id: rank 0 makes the 128-byte id (an ncclUniqueId) and hands it to the other ranks by the host's own
@@ -221,7 +226,19 @@ lm_status lm_merge_sharded(lm_index *idx, const lm_hsp *const *rows, const size_
  *     rank's count on every rank.  On `root`, *all_rows = the rows of rank 0, 1, ... back to back (pointer columns cleared:
  *     they are addresses of other processes; lm_merge_sharded re-attaches genome_id / seq_id), owned by the communicator
  *     and valid until its next call; elsewhere *all_rows = NULL.  All ranks must call it, in the same order.
- * RCCL is bound at run time (librccl.so.1; LM_RCCL_LIB overrides): a single-GPU user never loads it. */
+ * RCCL is bound at run time (librccl.so.1; LM_RCCL_LIB overrides): a single-GPU user never loads it.
+ *
+ * The _ex forms take the printer's flags: flags = 0 is the plain call, LM_ROW_ALL (-a/--all) makes the four string columns
+ * travel with their rows.  ALL RANKS MUST PASS THE SAME FLAGS: every rank's flags go with its row count, and on a mismatch
+ * (or a bit other than LM_ROW_ALL) every rank returns LM_ERR_ARG.  With LM_ROW_ALL the root's rows carry cigar / qseq / sseq /
+ * align pointers into a pinned host buffer owned by the communicator, valid until its next call (the lifetime of the rows); a
+ * NULL string comes back NULL, "" comes back "".
+ *   Wire form of the strings: per row four uint32 lengths (0xFFFFFFFF = NULL) and one block `cigar\0qseq\0sseq\0align\0` (a
+ *   NULL string takes no byte) zero-padded to a multiple of 16 bytes; the blocks of a rank's rows back to back in row order.
+ *   Each rank sends its rows, lengths and blocks as one group (16 bytes per row plus the padded strings beside the 168-byte
+ *   row).  The count exchange carries {rows, string bytes, flags and status} per rank - a rank that could not stage its
+ *   payload makes every rank fail - and, once the root has sized and allocated everything it receives into, a second
+ *   all-gather carries the root's go / no-go: if the root cannot receive, every rank returns LM_ERR_NOMEM and none waits. */
 #define LM_COMM_ID_BYTES 128
 typedef struct lm_comm lm_comm;
 lm_status lm_comm_unique_id(uint8_t id[LM_COMM_ID_BYTES]);
@@ -231,6 +248,9 @@ int lm_comm_rank(const lm_comm *comm);
 int lm_comm_size(const lm_comm *comm);
 const char *lm_comm_last_error(const lm_comm *comm); /* comm == NULL: the last failed lm_comm_unique_id / lm_comm_init of this thread */
 lm_status lm_gather_rows(lm_comm *comm, const lm_hsp *rows, size_t n, int root, const lm_hsp **all_rows, size_t *nrows);
+/* lm_gather_rows with flags (above).  With LM_ROW_ALL: rows' string pointers must be live in this process; on the root the
+ * gathered rows carry theirs (genome_id / seq_id still NULL), ready for lm_merge_sharded_ex(..., LM_ROW_ALL, ...). */
+lm_status lm_gather_rows_ex(lm_comm *comm, const lm_hsp *rows, size_t n, int root, int flags, const lm_hsp **all_rows, size_t *nrows);
 /* lm_gather_rows + lm_merge_sharded in one call, the merge on the DEVICE: the other ranks' rows are received into device memory
  * in rank order, the root's own are uploaded beside them, the final order (the reference's, as lm_merge_sharded makes it) and the
  * global `hits` are computed there and downloaded once.  On `root`: *merged = `*total` rows in output order with genome_id /
@@ -238,11 +258,24 @@ lm_status lm_gather_rows(lm_comm *comm, const lm_hsp *rows, size_t n, int root, 
  * elsewhere *merged = NULL and *total = 0.  All ranks must call it, in the same order. */
 lm_status lm_gather_merge_rows(lm_comm *comm, lm_index *idx, const lm_hsp *rows, size_t n, int root, const lm_hsp **merged,
                                size_t *total);
+/* lm_gather_merge_rows with flags (above).  With LM_ROW_ALL the lengths and blocks of all ranks are received into device memory
+ * in rank order beside the rows (borrowed from idx's scratch like the rows, else owned by the communicator), reordered there
+ * into the output order by the device merge, and downloaded once with the rows: *merged carries the string pointers. */
+lm_status lm_gather_merge_rows_ex(lm_comm *comm, lm_index *idx, const lm_hsp *rows, size_t n, int root, int flags, const lm_hsp **merged,
+                                  size_t *total);
 /* The merging rank's part of lm_gather_merge_rows by itself: d_rows = the rows of shard 0, 1, ... back to back in DEVICE memory
  * (nrows[r] each), merged on the device on the communicator's stream (a single-rank communicator will do), downloaded once,
  * names re-attached.  *merged / *total as above.  (How bench.py times the merge of N shards' rows on one GPU.) */
 lm_status lm_merge_sharded_device(lm_comm *comm, lm_index *idx, const void *d_rows, const size_t *nrows, int nshards,
                                   const lm_hsp **merged, size_t *total);
+/* lm_merge_sharded_device with flags.  flags = 0: d_strings and string_bytes are ignored (the plain call).  flags = LM_ROW_ALL:
+ * d_strings = the string columns of the rows of d_rows in DEVICE memory, in the wire form above, all shards back to back:
+ *     uint32 lens[total][4]        (total = the sum of nrows; shard order, then row order - as d_rows)
+ *     char   blocks[string_bytes]  at d_strings + 16 * total, 16-byte aligned (d_strings itself 16-byte aligned)
+ * string_bytes must be the sum of the rows' block sizes (LM_ERR_ARG otherwise, before anything is copied).  *merged carries
+ * the string pointers (into the communicator's pinned buffer, valid until its next call). */
+lm_status lm_merge_sharded_device_ex(lm_comm *comm, lm_index *idx, const void *d_rows, const size_t *nrows, const void *d_strings,
+                                     uint64_t string_bytes, int nshards, int flags, const lm_hsp **merged, size_t *total);
 
 /* -n/--top-n-genomes with a sharded index: the cut of lib-index-search.go:1781-1805 is over the genomes of ALL shards.
  *   1. every rank: lm_search_scores -> its candidates, per query at most top_n (query, genome, Chainer score)

@@ -180,6 +180,14 @@ def lib():
     L.lm_gather_rows.argtypes = [vp, C.POINTER(Hsp), C.c_size_t, C.c_int, C.POINTER(C.POINTER(Hsp)), C.POINTER(C.c_size_t)]
     L.lm_gather_merge_rows.argtypes = [vp, vp, C.POINTER(Hsp), C.c_size_t, C.c_int, C.POINTER(C.POINTER(Hsp)), C.POINTER(C.c_size_t)]
     L.lm_merge_sharded_device.argtypes = [vp, vp, vp, C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.POINTER(Hsp)), C.POINTER(C.c_size_t)]
+    L.lm_merge_sharded_ex.argtypes = [vp, C.POINTER(C.POINTER(Hsp)), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(vp)]
+    L.lm_gather_rows_ex.argtypes = [vp, C.POINTER(Hsp), C.c_size_t, C.c_int, C.c_int, C.POINTER(C.POINTER(Hsp)), C.POINTER(C.c_size_t)]
+    L.lm_gather_merge_rows_ex.argtypes = [vp, vp, C.POINTER(Hsp), C.c_size_t, C.c_int, C.c_int, C.POINTER(C.POINTER(Hsp)),
+                                          C.POINTER(C.c_size_t)]
+    L.lm_merge_sharded_device_ex.argtypes = [vp, vp, vp, C.POINTER(C.c_size_t), vp, C.c_uint64, C.c_int, C.c_int,
+                                             C.POINTER(C.POINTER(Hsp)), C.POINTER(C.c_size_t)]
+    L.lm_tsv_header.argtypes = [C.c_int]
+    L.lm_tsv_header.restype = C.c_char_p
     _lib = L
     return L
 
@@ -296,14 +304,32 @@ class Index:
         """rows as a numpy structured array VIEW of the library's lm_hsp rows (no copy; the lm_result is released when
         the array is garbage collected) + stats. The six `char *` columns are process-local addresses (valid while the
         array / the index are alive); lexicmap_amd.merge zeroes them before rows leave the process."""
-        import weakref
-        import numpy as np
-        from .merge import ROW_DTYPE
         L = lib()
         res = C.c_void_p()
         st = L.lm_search_resident(self.h, qb, C.byref(res))
         if st != 0:
             self._err(st)
+        return self._view(res)
+
+    def search_resident_keep_np(self, qb, keep_query, keep_bg):
+        """search_resident_keep with the rows as search_resident_np gives them: a numpy VIEW whose pointer columns are live
+        while the array is alive (what a sharded -n search hands to Comm.gather_merge_rows(strings=True))"""
+        import numpy as np
+        L = lib()
+        kq = np.ascontiguousarray(keep_query, dtype=np.uint32)
+        kg = np.ascontiguousarray(keep_bg, dtype=np.uint64)
+        res = C.c_void_p()
+        st = L.lm_search_resident_keep(self.h, qb, kq.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                       kg.ctypes.data_as(C.POINTER(C.c_uint64)), len(kq), C.byref(res))
+        if st != 0:
+            self._err(st)
+        return self._view(res)
+
+    def _view(self, res):
+        import weakref
+        import numpy as np
+        from .merge import ROW_DTYPE
+        L = lib()
         rows_p = C.POINTER(Hsp)()
         n = L.lm_result_rows(res, C.byref(rows_p))
         stats = StageStats()
@@ -531,6 +557,19 @@ def row_names(rows, i):
     return tuple(out)
 
 
+def row_strings(rows, i):
+    """(cigar, qseq, sseq, align) of row i of a numpy row array (merge.ROW_DTYPE) whose pointer columns are live in THIS
+    process; a NULL column is None"""
+    out = []
+    for f in ("cigar", "qseq", "sseq", "align"):
+        a = int(rows[f][i])
+        out.append(C.string_at(a).decode() if a else None)
+    return tuple(out)
+
+
+LM_ROW_ALL = 1  # include/lexicmap_hip.h: -a/--all, the four string columns (also the flag of the gather and merge calls)
+
+
 COMM_ID_BYTES = 128
 
 
@@ -561,15 +600,18 @@ class Comm:
             self.L.lm_comm_free(self.h)
             self.h = None
 
-    def gather_rows(self, arr, root=0):
+    def gather_rows(self, arr, root=0, strings=False):
         """arr: numpy rows of merge.ROW_DTYPE (this rank's).  -> (list of per-rank row arrays on `root` - views of the
-        communicator's buffer, valid until the next call - or None elsewhere, the per-rank counts)"""
+        communicator's buffer, valid until the next call - or None elsewhere, the per-rank counts).  strings=True (every rank
+        alike): the cigar / qseq / sseq / align of arr must be live in this process (e.g. search_resident_np's rows, kept alive
+        meanwhile); on `root` the rows' string columns then point into the communicator's buffer (api.row_strings)."""
         import numpy as np
         from .merge import ROW_DTYPE
         arr = np.ascontiguousarray(arr, dtype=ROW_DTYPE)
         allp = C.POINTER(Hsp)()
         cnt = (C.c_size_t * self.nranks)()
-        st = self.L.lm_gather_rows(self.h, arr.ctypes.data_as(C.POINTER(Hsp)), len(arr), root, C.byref(allp), cnt)
+        st = self.L.lm_gather_rows_ex(self.h, arr.ctypes.data_as(C.POINTER(Hsp)), len(arr), root, LM_ROW_ALL if strings else 0,
+                                      C.byref(allp), cnt)
         if st != 0:
             raise RuntimeError("lm_gather_rows failed (%d): %s" % (st, (self.L.lm_comm_last_error(self.h) or b"").decode()))
         counts = [int(x) for x in cnt]
@@ -586,16 +628,23 @@ class Comm:
             o += n
         return out, counts
 
-    def merge_sharded_device(self, dev_ptr, counts, index=None):
+    def merge_sharded_device(self, dev_ptr, counts, index=None, strings_ptr=None, string_bytes=0):
         """lm_merge_sharded_device: rows of shard 0, 1, ... back to back in device memory at address dev_ptr (counts[r] rows each)
-        -> the merged rows (a view of the communicator's pinned buffer, valid until its next call)"""
+        -> the merged rows (a view of the communicator's pinned buffer, valid until its next call).  strings_ptr (a device
+        address): the rows' string columns in the wire form of lm_merge_sharded_device_ex (include/lexicmap_hip.h) - uint32
+        lengths [total][4], then string_bytes of 16-byte blocks - which then follow their rows (api.row_strings)."""
         import numpy as np
         from .merge import ROW_DTYPE
         outp = C.POINTER(Hsp)()
         total = C.c_size_t(0)
         cnt = (C.c_size_t * len(counts))(*[int(x) for x in counts])
-        st = self.L.lm_merge_sharded_device(self.h, index.h if index is not None else None, C.c_void_p(int(dev_ptr)), cnt, len(counts),
-                                            C.byref(outp), C.byref(total))
+        if strings_ptr is None:
+            st = self.L.lm_merge_sharded_device(self.h, index.h if index is not None else None, C.c_void_p(int(dev_ptr)), cnt, len(counts),
+                                                C.byref(outp), C.byref(total))
+        else:
+            st = self.L.lm_merge_sharded_device_ex(self.h, index.h if index is not None else None, C.c_void_p(int(dev_ptr)), cnt,
+                                                   C.c_void_p(int(strings_ptr)), int(string_bytes), len(counts), LM_ROW_ALL,
+                                                   C.byref(outp), C.byref(total))
         if st != 0:
             raise RuntimeError("lm_merge_sharded_device failed (%d): %s" % (st, (self.L.lm_comm_last_error(self.h) or b"").decode()))
         if total.value == 0:
@@ -603,17 +652,18 @@ class Comm:
         buf = (C.c_char * (total.value * C.sizeof(Hsp))).from_address(C.addressof(outp.contents))
         return np.frombuffer(buf, dtype=ROW_DTYPE)
 
-    def gather_merge_rows(self, arr, root=0, index=None):
+    def gather_merge_rows(self, arr, root=0, index=None, strings=False):
         """lm_gather_merge_rows: the gather and the merge (on the device) in one call.  -> on `root` the merged rows of all ranks
         in output order (a view of the communicator's pinned buffer, valid until its next call), None elsewhere.  index: the
-        root's Index (names are re-attached from it) or None."""
+        root's Index (names are re-attached from it) or None.  strings=True (every rank alike): the string columns of arr
+        (live in this process) travel too and the merged rows carry them (api.row_strings, api.format_rows with LM_ROW_ALL)."""
         import numpy as np
         from .merge import ROW_DTYPE
         arr = np.ascontiguousarray(arr, dtype=ROW_DTYPE)
         outp = C.POINTER(Hsp)()
         total = C.c_size_t(0)
-        st = self.L.lm_gather_merge_rows(self.h, index.h if index is not None else None, arr.ctypes.data_as(C.POINTER(Hsp)), len(arr), root,
-                                         C.byref(outp), C.byref(total))
+        st = self.L.lm_gather_merge_rows_ex(self.h, index.h if index is not None else None, arr.ctypes.data_as(C.POINTER(Hsp)), len(arr),
+                                            root, LM_ROW_ALL if strings else 0, C.byref(outp), C.byref(total))
         if st != 0:
             raise RuntimeError("lm_gather_merge_rows failed (%d): %s" % (st, (self.L.lm_comm_last_error(self.h) or b"").decode()))
         if self.rank != root:

@@ -15,6 +15,16 @@
 //   k_mg_qruns   groups per query = hits; scan of the group sizes in sorted order = output positions
 //   k_mg_emit    one thread per output row: its group by binary search over the positions, the row copied with hits set and
 //                the pointer columns cleared (addresses of other processes)
+// With the string columns (MergeStrings: lengths + 16-byte blocks in the wire form of lm_merge.h, rank order like the rows):
+//   scan           block offsets of the input rows - ranks and blobs are both in rank-then-row order, so ONE scan over all rows;
+//                  its total is checked against the bytes that arrived before anything is copied
+//   k_mg_emit<1>   k_mg_emit + the source row of every output row
+//   scan           block offsets in output order (the same sizes, permuted)
+//   k_mg_copy_head one wavefront per output row: the first kMgChunk bytes of its block (64 lanes x 16 B per step, both sides
+//                  16-byte aligned) and its four pointers, written as HOST addresses into the pinned buffer the blocks are
+//                  downloaded into - no host pass over the rows after the download
+//   k_mg_copy_tail the rest of the blocks longer than kMgChunk, one kMgChunk per wavefront (a 300-kb HSP makes a 0.9-MB block):
+//                  grid-stride over the tail chunks, counted by an inclusive scan
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -89,8 +99,9 @@ __global__ void k_mg_qruns(const MgKey *__restrict__ keys, int64_t ng, const uin
     while (e < ng && keys[e].q == keys[p].q) e++;
     for (int64_t x = p; x < e; x++) hits[x] = (uint32_t)(e - p);
 }
+template <bool kSrc>
 __global__ void k_mg_emit(const lm_hsp *__restrict__ rows, int64_t n, const MgKey *__restrict__ keys, int64_t ng, const uint32_t *__restrict__ first,
-                          const int64_t *__restrict__ outpos, const uint32_t *__restrict__ hits, lm_hsp *__restrict__ out) {
+                          const int64_t *__restrict__ outpos, const uint32_t *__restrict__ hits, lm_hsp *__restrict__ out, uint32_t *__restrict__ src) {
     const int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (o >= n) return;
     int64_t lo = 0, hi = ng; // last p with outpos[p] <= o
@@ -102,11 +113,94 @@ __global__ void k_mg_emit(const lm_hsp *__restrict__ rows, int64_t n, const MgKe
             hi = mid;
     }
     const uint32_t g = keys[lo].g;
-    lm_hsp h = rows[(int64_t)first[g] + (o - outpos[lo])];
+    const int64_t s = (int64_t)first[g] + (o - outpos[lo]);
+    lm_hsp h = rows[s];
     h.hits = hits[lo];
     h.genome_id = h.seq_id = nullptr; // addresses of another process: the host re-attaches the names
     h.cigar = h.qseq = h.sseq = h.align = nullptr;
     out[o] = h;
+    if (kSrc) src[o] = (uint32_t)s;
+}
+
+// ---- the string columns ----
+constexpr int64_t kMgChunk = 64 * 1024; // bytes of a block one wavefront copies (the head, then each tail chunk)
+
+struct MgBlockIn { // block bytes of input row i; 0 at i = n (the n+1-th item of the scan gives the total)
+    const uint32_t *lens;
+    int64_t n;
+    __host__ __device__ int64_t operator()(const int64_t &i) const { return i < n ? (int64_t)block_bytes(lens + 4 * i) : 0; }
+};
+struct MgBlockOut { // block bytes of output row o
+    const uint32_t *lens, *src;
+    __host__ __device__ int64_t operator()(const int64_t &o) const { return (int64_t)block_bytes(lens + 4 * (int64_t)src[o]); }
+};
+struct MgTailChunks { // chunks of output row o after its head
+    const uint32_t *lens, *src;
+    __host__ __device__ int64_t operator()(const int64_t &o) const {
+        const int64_t b = (int64_t)block_bytes(lens + 4 * (int64_t)src[o]);
+        return b > kMgChunk ? (b - 1) / kMgChunk : 0;
+    }
+};
+
+// one wavefront copies `bytes` (a multiple of 16) from s to d, both 16-byte aligned: 64 lanes x 16 B per step, four steps in flight
+__device__ __forceinline__ void mg_copy_wave(const char *__restrict__ s, char *__restrict__ d, int64_t bytes, int lane) {
+    const uint4 *a = (const uint4 *)s;
+    uint4 *b = (uint4 *)d;
+    const int64_t n = bytes >> 4;
+    int64_t i = lane;
+    for (; i + 192 < n; i += 256) {
+        const uint4 x0 = a[i], x1 = a[i + 64], x2 = a[i + 128], x3 = a[i + 192];
+        b[i] = x0;
+        b[i + 64] = x1;
+        b[i + 128] = x2;
+        b[i + 192] = x3;
+    }
+    for (; i < n; i += 64) b[i] = a[i];
+}
+
+__global__ void k_mg_copy_head(const uint32_t *__restrict__ lens, const uint32_t *__restrict__ src, const int64_t *__restrict__ soff,
+                               const int64_t *__restrict__ doff, int64_t n, const char *__restrict__ in, char *__restrict__ out, uint64_t host,
+                               lm_hsp *__restrict__ rows) {
+    const int64_t o = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (o >= n) return;
+    const uint32_t *l = lens + 4 * (int64_t)src[o];
+    const int64_t bytes = (int64_t)block_bytes(l);
+    if (bytes == 0) return; // four NULL strings: k_mg_emit cleared the pointers
+    const int64_t d0 = doff[o];
+    mg_copy_wave(in + soff[src[o]], out + d0, bytes < kMgChunk ? bytes : kMgChunk, lane);
+    if (lane < 4) {
+        uint64_t at = host + (uint64_t)d0;
+        for (int k = 0; k < lane; k++) at += str_bytes(l[k]);
+        const char *p = l[lane] == kStrNull ? nullptr : (const char *)at;
+        lm_hsp &r = rows[o];
+        if (lane == 0) r.cigar = p;
+        else if (lane == 1) r.qseq = p;
+        else if (lane == 2) r.sseq = p;
+        else r.align = p;
+    }
+}
+
+__global__ void k_mg_copy_tail(const uint32_t *__restrict__ lens, const uint32_t *__restrict__ src, const int64_t *__restrict__ soff,
+                               const int64_t *__restrict__ doff, const int64_t *__restrict__ xend, int64_t n, const char *__restrict__ in,
+                               char *__restrict__ out) {
+    const int64_t total = xend[n - 1];
+    const int lane = threadIdx.x & 63;
+    const int64_t nw = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t c = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); c < total; c += nw) {
+        int64_t lo = 0, hi = n - 1; // the output row of tail chunk c: first o with xend[o] > c
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (xend[mid] > c)
+                hi = mid;
+            else
+                lo = mid + 1;
+        }
+        const uint32_t s = src[lo];
+        const int64_t bytes = (int64_t)block_bytes(lens + 4 * (int64_t)s);
+        const int64_t b0 = (1 + c - (xend[lo] - (bytes - 1) / kMgChunk)) * kMgChunk;
+        mg_copy_wave(in + soff[s] + b0, out + doff[lo] + b0, bytes - b0 < kMgChunk ? bytes - b0 : kMgChunk, lane);
+    }
 }
 
 #define MG_HIP(expr)                        \
@@ -116,7 +210,7 @@ __global__ void k_mg_emit(const lm_hsp *__restrict__ rows, int64_t n, const MgKe
     } while (0)
 
 void *MergeScratch::take(size_t bytes) {
-    if (!borrow || nborrowed >= 16) return nullptr;
+    if (!borrow || nborrowed >= 32) return nullptr;
     void *p = borrow(ctx, bytes);
     if (p) borrowed[nborrowed++] = p;
     return p;
@@ -125,7 +219,7 @@ void MergeScratch::end_call() {
     if (!borrow) return;
     for (int i = 0; i < nborrowed; i++) give_back(ctx, borrowed[i]);
     nborrowed = 0;
-    void **ps[] = {&head, &gid, &sim, &keys, &keys2, &first, &cnt, &sizes, &hits, &outpos, &tmp, &off};
+    void **ps[] = {&head, &gid, &sim, &keys, &keys2, &first, &cnt, &sizes, &hits, &outpos, &tmp, &off, &src, &soff, &doff, &xend};
     for (void **p : ps) *p = nullptr;
     for (size_t &c : cap) c = 0;
     borrow = nullptr;
@@ -154,7 +248,7 @@ void MergeScratch::release() {
         end_call();
         return;
     }
-    void **ps[] = {&head, &gid, &sim, &keys, &keys2, &first, &cnt, &sizes, &hits, &outpos, &tmp, &off};
+    void **ps[] = {&head, &gid, &sim, &keys, &keys2, &first, &cnt, &sizes, &hits, &outpos, &tmp, &off, &src, &soff, &doff, &xend};
     for (void **p : ps) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
@@ -163,8 +257,10 @@ void MergeScratch::release() {
 }
 
 // d_rows: the rows of rank 0, 1, ... back to back (rank r at [off[r], off[r + 1]), each block grouped by query ascending, a
-// genome's rows together); d_out: n rows in the final order.  Everything on `st`; returns when the work is QUEUED.
-hipError_t merge_rows_device(hipStream_t st, const lm_hsp *d_rows, size_t n, const int64_t *off_host, int nranks, lm_hsp *d_out, MergeScratch &S) {
+// genome's rows together); d_out: n rows in the final order; str: the string columns (lm_merge.h) or NULL.  Everything on `st`;
+// returns when the work is QUEUED.
+hipError_t merge_rows_device(hipStream_t st, const lm_hsp *d_rows, size_t n, const int64_t *off_host, int nranks, lm_hsp *d_out, MergeScratch &S,
+                             const MergeStrings *str) {
     if (n == 0) return hipSuccess;
     if (n >= ((size_t)1 << 32)) return hipErrorInvalidValue;
     const int64_t N = (int64_t)n;
@@ -180,9 +276,24 @@ hipError_t merge_rows_device(hipStream_t st, const lm_hsp *d_rows, size_t n, con
     MG_HIP(rocprim::inclusive_scan(nullptr, bytes, (uint32_t *)S.head, (uint32_t *)S.gid, n, rocprim::plus<uint32_t>(), st));
     MG_HIP(mg_grow(S, &S.tmp, &S.cap[10], bytes));
     MG_HIP(rocprim::inclusive_scan(S.tmp, bytes, (uint32_t *)S.head, (uint32_t *)S.gid, n, rocprim::plus<uint32_t>(), st));
+    const bool strs = str && str->bytes > 0; // (no byte: every string is NULL, and so are the cleared pointers)
+    int64_t in_bytes = 0;
+    if (str) {
+        if (!str->lens) return hipErrorInvalidValue;
+        // block offsets of the input rows: n + 1 items, the last one 0, so that soff[n] = the bytes the lengths describe
+        MG_HIP(mg_grow(S, &S.soff, &S.cap[13], (n + 1) * 8));
+        auto it = rocprim::make_transform_iterator(rocprim::make_counting_iterator<int64_t>(0), MgBlockIn{str->lens, N});
+        bytes = 0;
+        MG_HIP(rocprim::exclusive_scan(nullptr, bytes, it, (int64_t *)S.soff, (int64_t)0, n + 1, rocprim::plus<int64_t>(), st));
+        MG_HIP(mg_grow(S, &S.tmp, &S.cap[10], bytes));
+        MG_HIP(rocprim::exclusive_scan(S.tmp, bytes, it, (int64_t *)S.soff, (int64_t)0, n + 1, rocprim::plus<int64_t>(), st));
+        MG_HIP(hipMemcpyAsync(&in_bytes, (int64_t *)S.soff + n, 8, hipMemcpyDeviceToHost, st));
+    }
     uint32_t ng32 = 0;
     MG_HIP(hipMemcpyAsync(&ng32, (uint32_t *)S.gid + (n - 1), 4, hipMemcpyDeviceToHost, st));
     MG_HIP(hipStreamSynchronize(st)); // (the number of groups sizes what follows)
+    if (str && (uint64_t)in_bytes != str->bytes) return hipErrorInvalidValue; // the lengths do not describe the blocks that arrived
+    if (strs && (!str->in || !str->out)) return hipErrorInvalidValue;
     const size_t ng = ng32;
     MG_HIP(mg_grow(S, &S.keys, &S.cap[3], ng * sizeof(MgKey)));
     MG_HIP(mg_grow(S, &S.keys2, &S.cap[4], ng * sizeof(MgKey)));
@@ -191,6 +302,11 @@ hipError_t merge_rows_device(hipStream_t st, const lm_hsp *d_rows, size_t n, con
     MG_HIP(mg_grow(S, &S.sizes, &S.cap[7], ng * 4));
     MG_HIP(mg_grow(S, &S.hits, &S.cap[8], ng * 4));
     MG_HIP(mg_grow(S, &S.outpos, &S.cap[9], (ng + 1) * 8));
+    if (strs) {
+        MG_HIP(mg_grow(S, &S.src, &S.cap[12], n * 4));
+        MG_HIP(mg_grow(S, &S.doff, &S.cap[14], n * 8));
+        MG_HIP(mg_grow(S, &S.xend, &S.cap[15], n * 8));
+    }
     hipLaunchKernelGGL(k_mg_groups, dim3(gb), dim3(B), 0, st, d_rows, N, (const uint32_t *)S.head, (const uint32_t *)S.gid, (const double *)S.sim,
                        (MgKey *)S.keys, (uint32_t *)S.first, (uint32_t *)S.cnt);
     bytes = 0;
@@ -205,8 +321,31 @@ hipError_t merge_rows_device(hipStream_t st, const lm_hsp *d_rows, size_t n, con
     MG_HIP(rocprim::exclusive_scan(nullptr, bytes, it, (int64_t *)S.outpos, (int64_t)0, ng, rocprim::plus<int64_t>(), st));
     MG_HIP(mg_grow(S, &S.tmp, &S.cap[10], bytes));
     MG_HIP(rocprim::exclusive_scan(S.tmp, bytes, it, (int64_t *)S.outpos, (int64_t)0, ng, rocprim::plus<int64_t>(), st));
-    hipLaunchKernelGGL(k_mg_emit, dim3(gb), dim3(B), 0, st, d_rows, N, (const MgKey *)S.keys2, (int64_t)ng, (const uint32_t *)S.first,
-                       (const int64_t *)S.outpos, (const uint32_t *)S.hits, d_out);
+    if (!strs) {
+        hipLaunchKernelGGL(k_mg_emit<false>, dim3(gb), dim3(B), 0, st, d_rows, N, (const MgKey *)S.keys2, (int64_t)ng, (const uint32_t *)S.first,
+                           (const int64_t *)S.outpos, (const uint32_t *)S.hits, d_out, (uint32_t *)nullptr);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(k_mg_emit<true>, dim3(gb), dim3(B), 0, st, d_rows, N, (const MgKey *)S.keys2, (int64_t)ng, (const uint32_t *)S.first,
+                       (const int64_t *)S.outpos, (const uint32_t *)S.hits, d_out, (uint32_t *)S.src);
+    // block offsets in output order, and the tail chunks of the blocks longer than kMgChunk
+    const uint32_t *src = (const uint32_t *)S.src;
+    auto ob = rocprim::make_transform_iterator(rocprim::make_counting_iterator<int64_t>(0), MgBlockOut{str->lens, src});
+    bytes = 0;
+    MG_HIP(rocprim::exclusive_scan(nullptr, bytes, ob, (int64_t *)S.doff, (int64_t)0, n, rocprim::plus<int64_t>(), st));
+    MG_HIP(mg_grow(S, &S.tmp, &S.cap[10], bytes));
+    MG_HIP(rocprim::exclusive_scan(S.tmp, bytes, ob, (int64_t *)S.doff, (int64_t)0, n, rocprim::plus<int64_t>(), st));
+    auto tc = rocprim::make_transform_iterator(rocprim::make_counting_iterator<int64_t>(0), MgTailChunks{str->lens, src});
+    bytes = 0;
+    MG_HIP(rocprim::inclusive_scan(nullptr, bytes, tc, (int64_t *)S.xend, n, rocprim::plus<int64_t>(), st));
+    MG_HIP(mg_grow(S, &S.tmp, &S.cap[10], bytes));
+    MG_HIP(rocprim::inclusive_scan(S.tmp, bytes, tc, (int64_t *)S.xend, n, rocprim::plus<int64_t>(), st));
+    const int W = B / 64; // wavefronts per workgroup
+    hipLaunchKernelGGL(k_mg_copy_head, dim3((unsigned)((n + W - 1) / W)), dim3(B), 0, st, str->lens, src, (const int64_t *)S.soff,
+                       (const int64_t *)S.doff, N, str->in, str->out, str->host, d_out);
+    // (a fixed grid: 4 wavefronts on each of 256 CUs x 2; it finds the number of tail chunks on the device, usually none)
+    hipLaunchKernelGGL(k_mg_copy_tail, dim3(512), dim3(B), 0, st, str->lens, src, (const int64_t *)S.soff, (const int64_t *)S.doff,
+                       (const int64_t *)S.xend, N, str->in, str->out);
     return hipGetLastError();
 }
 

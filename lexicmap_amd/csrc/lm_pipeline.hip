@@ -4002,8 +4002,15 @@ void lm_attach_names(lm_index *ix, lm_hsp *rows, size_t n) {
 // ---- merging the rows of genome shards ------------------------------------------------------------
 // Host-only: no device work, callable without a GPU (idx may be NULL: names are then left NULL).
 lm_status lm_merge_sharded(lm_index *ix, const lm_hsp *const *rows, const size_t *nrows, int nshards, lm_result **out) {
+    return lm_merge_sharded_ex(ix, rows, nrows, nshards, 0, out);
+}
+// flags = LM_ROW_ALL: the string columns of the input rows are live in this process and are copied, in output order, into ONE
+// buffer the result owns (one allocation, not four per row)
+lm_status lm_merge_sharded_ex(lm_index *ix, const lm_hsp *const *rows, const size_t *nrows, int nshards, int flags, lm_result **out) {
+    if (!out) return LM_ERR_ARG;
     *out = nullptr;
-    if (nshards < 1 || !rows || !nrows) return LM_ERR_ARG;
+    if (nshards < 1 || !rows || !nrows || (flags & ~LM_ROW_ALL)) return LM_ERR_ARG;
+    const bool strs = (flags & LM_ROW_ALL) != 0;
     lm_result *res = new lm_result();
     try {
         memset(&res->stats, 0, sizeof res->stats);
@@ -4056,6 +4063,7 @@ lm_status lm_merge_sharded(lm_index *ix, const lm_hsp *const *rows, const size_t
             }
         }
         res->rows.resize(total);
+        std::vector<const lm_hsp *> src(strs ? total : 0); // the input row of every output row
         parallel_for((int64_t)jobs.size(), 16, [&](int64_t j0, int64_t j1) {
             struct Grp {
                 int rank;
@@ -4094,10 +4102,37 @@ lm_status lm_merge_sharded(lm_index *ix, const lm_hsp *const *rows, const size_t
                         h.genome_id = h.seq_id = nullptr;
                         h.cigar = h.qseq = h.sseq = h.align = nullptr; // process-local addresses of another rank
                         if (ix) attach_name(ix, h);
+                        if (strs) src[w] = &rows[g.rank][i];
                         res->rows[w++] = h;
                     }
             }
         });
+        if (strs && total > 0) { // the strings of every output row, back to back in output order (NULL stays NULL, "" stays "")
+            std::vector<uint64_t> at(total + 1, 0);
+            for (size_t o = 0; o < total; o++) {
+                uint64_t b = 0;
+                for (const char *p : {src[o]->cigar, src[o]->qseq, src[o]->sseq, src[o]->align})
+                    if (p) b += strlen(p) + 1;
+                at[o + 1] = at[o] + b;
+            }
+            std::string *blob = new std::string(std::max<uint64_t>(at[total], 1), '\0');
+            res->strings.push_back(blob);
+            char *base = &(*blob)[0];
+            parallel_for((int64_t)total, 1024, [&](int64_t o0, int64_t o1) {
+                for (int64_t o = o0; o < o1; o++) {
+                    char *d = base + at[(size_t)o];
+                    const char *in[4] = {src[(size_t)o]->cigar, src[(size_t)o]->qseq, src[(size_t)o]->sseq, src[(size_t)o]->align};
+                    const char **dst[4] = {&res->rows[(size_t)o].cigar, &res->rows[(size_t)o].qseq, &res->rows[(size_t)o].sseq, &res->rows[(size_t)o].align};
+                    for (int k = 0; k < 4; k++) {
+                        if (!in[k]) continue;
+                        const size_t b = strlen(in[k]) + 1;
+                        memcpy(d, in[k], b);
+                        *dst[k] = d;
+                        d += b;
+                    }
+                }
+            });
+        }
         res->stats.rows = (int64_t)res->rows.size();
     } catch (const std::exception &e) {
         if (ix) ix->err = e.what();

@@ -140,24 +140,27 @@ def merge_query_sharded(per_rank):
     return out
 
 
-def merge_sharded_c(per_rank, index=None):
+def merge_sharded_c(per_rank, index=None, strings=False):
     """the same merge through the library's C entry point lm_merge_sharded (what a Go host calls); `index` (an
-    lexicmap_amd.Index or None) re-attaches genome / sequence names. Returns a fresh row array."""
+    lexicmap_amd.Index or None) re-attaches genome / sequence names. Returns a fresh row array.
+    strings=True (lm_merge_sharded_ex with LM_ROW_ALL): the string columns of the input rows must be live in this process
+    (e.g. Comm.gather_rows(strings=True)); they are copied into the result, and the return value is then a view of it whose
+    pointer columns - names included, when `index` is given - stay live while the array is (api.row_strings, api.row_names)."""
     import ctypes as C
-    from .api import Hsp, lib
+    from .api import Hsp, LM_ROW_ALL, lib
     L = lib()
     arrs = [np.ascontiguousarray(p, dtype=ROW_DTYPE) for p in per_rank]
     n = len(arrs)
     ptrs = (C.POINTER(Hsp) * n)(*[a.ctypes.data_as(C.POINTER(Hsp)) for a in arrs])
     cnts = (C.c_size_t * n)(*[len(a) for a in arrs])
     res = C.c_void_p()
-    st = L.lm_merge_sharded(index.h if index is not None else None, ptrs, cnts, n, C.byref(res))
+    st = L.lm_merge_sharded_ex(index.h if index is not None else None, ptrs, cnts, n, LM_ROW_ALL if strings else 0, C.byref(res))
     if st != 0:
         raise RuntimeError("lm_merge_sharded failed (%d)" % st)
     rows_p = C.POINTER(Hsp)()
     k = L.lm_result_rows(res, C.byref(rows_p))
-    if index is None:
-        # a view of the library's result (its pointer columns are NULL without an index): no copy of the merged rows - at
+    if index is None or strings:
+        # a view of the library's result (its pointer columns are NULL without an index and strings): no copy of the merged rows - at
         # 8 shards x 6e5 rows the copy out and the six strided column writes were a third of the host-side merge
         if not k:
             L.lm_result_free(res)
@@ -175,6 +178,28 @@ def merge_sharded_c(per_rank, index=None):
     for f in PTR_FIELDS:
         out[f] = 0
     return out, names
+
+
+STR_NULL = 0xFFFFFFFF  # the length of a NULL string in the wire form
+
+
+def pack_strings(strs):
+    """the wire form of the string columns (include/lexicmap_hip.h, lm_merge_sharded_device_ex): strs = per row a 4-tuple
+    (cigar, qseq, sseq, align) of bytes or None -> (lengths uint32 [n, 4], the rows' blocks back to back as bytes): a row's
+    block is cigar\\0qseq\\0sseq\\0align\\0 without its NULL strings, zero-padded to a multiple of 16 bytes"""
+    lens = np.zeros((len(strs), 4), dtype=np.uint32)
+    parts = []
+    for i, row in enumerate(strs):
+        blk = []
+        for k, x in enumerate(row):
+            if x is None:
+                lens[i, k] = STR_NULL
+            else:
+                lens[i, k] = len(x)
+                blk += [x, b"\0"]
+        b = b"".join(blk)
+        parts.append(b + b"\0" * (-len(b) % 16))
+    return lens, b"".join(parts)
 
 
 def topn_merge(cands, top_n):
