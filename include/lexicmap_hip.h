@@ -67,7 +67,7 @@ typedef struct lm_index_info {
     int64_t genomes;       /* genomes resident on this device */
     int64_t seeds;         /* (k-mer,value) pairs resident on this device */
     int64_t genome_bases;  /* concatenated bases resident on this device */
-    int64_t hbm_bytes;     /* device memory held by the index image (seeds + genomes + tables) */
+    int64_t hbm_bytes;     /* device memory held by the index image (seeds + device-resident genomes + tables) */
     int64_t seed_bytes;    /* device memory of the packed seed image alone (partition tables + key and value streams) */
     int64_t outlier_seeds; /* seeds kept in the flat 16-byte form (k-mer does not start with its mask's prefix) */
     int32_t key_bits, val_bits, partition_bases; /* packed seed layout: bits per k-mer remainder / value, bases per partition */
@@ -99,6 +99,31 @@ typedef struct lm_synth_spec {
     int32_t seed_dist;    /* 50 (index.go:584) */
 } lm_synth_spec;
 lm_status lm_index_build_synthetic(const lm_synth_spec *spec, const lm_options *opt, int device, lm_index **out);
+/* Residency of the 2-bit genomes (residency).  The seed image is always in HBM; the genomes are too when they fit,
+ * else - or on request - they live in pinned host memory and a search copies the byte ranges of its chain windows to the
+ * device (k_stage_genome_bits).  Rows are the same wherever a genome lives.
+ *   LM_GENOMES_DEVICE: every genome in HBM (the open / build fails when the store does not fit);
+ *   LM_GENOMES_HOST:   every genome in pinned host memory;
+ *   LM_GENOMES_AUTO:   genomes in local order go to HBM while genome_hbm_bytes last (padding counted), the first that does
+ *                      not fit and all after it to pinned host memory; a genome is never split.  genome_hbm_bytes = 0: the
+ *                      budget is the free device memory beside the seed image minus a scratch floor and a 3-GB reserve.
+ * res == NULL (and the plain lm_index_open / lm_index_build_synthetic) = AUTO with budget 0: everything in HBM whenever it fits.
+ * LM_GENOME_PLACEMENT=auto|device|host and LM_GENOME_HBM_MB=<n> (measurement only, read at open / build) stand in for a NULL
+ * res; a non-NULL res wins.  A pinned allocation the host refuses is LM_ERR_NOMEM; an unknown `genomes` value LM_ERR_OPTION. */
+enum { LM_GENOMES_AUTO = 0, LM_GENOMES_DEVICE = 1, LM_GENOMES_HOST = 2 };
+typedef struct lm_residency {
+    int32_t genomes;            /* LM_GENOMES_* */
+    int32_t pad;
+    int64_t genome_hbm_bytes;   /* AUTO: device bytes the genome store may take; 0 = derive from free HBM */
+} lm_residency;
+typedef struct lm_residency_info {
+    int64_t genomes_device, genomes_host;
+    int64_t genome_bytes_device, genome_bytes_host;   /* 2-bit bytes incl. padding */
+    int64_t stage_bytes;        /* device staging buffer(s) currently held for host-resident windows */
+} lm_residency_info;
+lm_status lm_index_open_ex(const char *dir, const lm_options *opt, const lm_residency *res, int device, lm_index **out);
+lm_status lm_index_build_synthetic_ex(const lm_synth_spec *spec, const lm_options *opt, const lm_residency *res, int device, lm_index **out);
+lm_status lm_index_get_residency(const lm_index *idx, lm_residency_info *info);
 /* bases [start, start+len) of local genome `local_genome` as ASCII (used to derive synthetic queries) */
 lm_status lm_index_fetch(lm_index *idx, int64_t local_genome, int64_t start, int64_t len, uint8_t *out);
 /* Writes the resident (unsharded) index to `dir`: info.toml, seeds/chunk_NNN.bin (+ .idx, kv/kv-data.go:126-602) in at most

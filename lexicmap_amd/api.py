@@ -88,6 +88,22 @@ class SynthSpec(C.Structure):
                 ("max_desert", C.c_int32), ("seed_dist", C.c_int32)]
 
 
+GENOMES_AUTO, GENOMES_DEVICE, GENOMES_HOST = 0, 1, 2  # lm_residency.genomes
+
+
+class Residency(C.Structure):
+    """lm_residency: where the 2-bit genomes live (HBM, pinned host memory, or HBM up to a byte budget)"""
+    _fields_ = [("genomes", C.c_int32), ("pad", C.c_int32), ("genome_hbm_bytes", C.c_int64)]
+
+    def __init__(self, genomes=GENOMES_AUTO, genome_hbm_bytes=0):
+        super().__init__(genomes, 0, genome_hbm_bytes)
+
+
+class ResidencyInfo(C.Structure):
+    _fields_ = [("genomes_device", C.c_int64), ("genomes_host", C.c_int64), ("genome_bytes_device", C.c_int64),
+                ("genome_bytes_host", C.c_int64), ("stage_bytes", C.c_int64)]
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char_p), ("launches", C.c_int64), ("total_ms", C.c_double), ("bytes", C.c_int64)]
 
@@ -115,6 +131,10 @@ def lib():
     vp = C.c_void_p
     L.lm_options_default.argtypes = [C.POINTER(Options)]
     L.lm_index_open.argtypes = [C.c_char_p, C.POINTER(Options), C.c_int, C.POINTER(vp)]
+    L.lm_index_open_ex.argtypes = [C.c_char_p, C.POINTER(Options), C.POINTER(Residency), C.c_int, C.POINTER(vp)]
+    L.lm_index_build_synthetic_ex.argtypes = [C.POINTER(SynthSpec), C.POINTER(Options), C.POINTER(Residency), C.c_int,
+                                              C.POINTER(vp)]
+    L.lm_index_get_residency.argtypes = [vp, C.POINTER(ResidencyInfo)]
     L.lm_index_close.argtypes = [vp]
     L.lm_index_get_info.argtypes = [vp, C.POINTER(IndexInfo)]
     L.lm_index_masks.argtypes = [vp]
@@ -214,29 +234,46 @@ def default_options(**kw):
 class Index:
     """lm_index handle (replaces cmd.NewIndexSearcher / Index.Search / Index.Close of the reference)."""
 
-    def __init__(self, path, options=None, device=0, _handle=None):
+    def __init__(self, path, options=None, device=0, _handle=None, residency=None):
+        """residency: a Residency (lm_index_open_ex); None makes the plain lm_index_open call"""
         L = lib()
         self.opt = options or default_options()
         if _handle is not None:
             self.h = _handle
             return
         h = C.c_void_p()
-        st = L.lm_index_open(path.encode(), C.byref(self.opt), device, C.byref(h))
+        if residency is None:
+            st = L.lm_index_open(path.encode(), C.byref(self.opt), device, C.byref(h))
+        else:
+            st = L.lm_index_open_ex(path.encode(), C.byref(self.opt), C.byref(residency), device, C.byref(h))
         if st != 0:
             raise RuntimeError("lm_index_open failed (%d): %s" % (st, L.lm_last_error(None).decode()))
         self.h = h
 
     @classmethod
-    def synthetic(cls, genomes, genome_len, families, seed=1000, max_div=0.10, masks=20000, options=None, device=0):
-        """genomes + seed index generated directly in HBM by lm_index_build_synthetic (bench input)"""
+    def synthetic(cls, genomes, genome_len, families, seed=1000, max_div=0.10, masks=20000, options=None, device=0,
+                  residency=None):
+        """genomes + seed index generated directly in HBM by lm_index_build_synthetic (bench input); residency as in
+        __init__ (the genomes beyond the device budget move to pinned host memory once the set is built)"""
         L = lib()
         opt = options or default_options()
         sp = SynthSpec(31, masks, 1, genomes, genome_len, families, max_div, seed, 100, 50)
         h = C.c_void_p()
-        st = L.lm_index_build_synthetic(C.byref(sp), C.byref(opt), device, C.byref(h))
+        if residency is None:
+            st = L.lm_index_build_synthetic(C.byref(sp), C.byref(opt), device, C.byref(h))
+        else:
+            st = L.lm_index_build_synthetic_ex(C.byref(sp), C.byref(opt), C.byref(residency), device, C.byref(h))
         if st != 0:
             raise RuntimeError("lm_index_build_synthetic failed (%d): %s" % (st, L.lm_last_error(None).decode()))
         return cls(None, opt, device, _handle=h)
+
+    def residency(self):
+        """lm_index_get_residency: genomes and 2-bit bytes on the device / in pinned host memory, staging bytes held"""
+        r = ResidencyInfo()
+        st = lib().lm_index_get_residency(self.h, C.byref(r))
+        if st != 0:
+            self._err(st)
+        return {f[0]: getattr(r, f[0]) for f in ResidencyInfo._fields_}
 
     def save(self, path, chunks=16):
         """the resident index written in the reference's on-disk format (lm_index_save)"""

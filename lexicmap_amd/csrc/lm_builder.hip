@@ -535,7 +535,15 @@ static void gen_masks(int k, int M, uint64_t seed, std::vector<uint64_t> &out) {
 extern "C" {
 
 lm_status lm_index_build_synthetic(const lm_synth_spec *spec, const lm_options *opt, int device, lm_index **out) {
+    return lm_index_build_synthetic_ex(spec, opt, nullptr, device, out);
+}
+lm_status lm_index_build_synthetic_ex(const lm_synth_spec *spec, const lm_options *opt, const lm_residency *res, int device, lm_index **out) {
     *out = nullptr;
+    lm_res_request rq;
+    {
+        const lm_status rs = lm_res_resolve(res, rq, g_open_error);
+        if (rs != LM_OK) return rs;
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
         g_open_error = "no HIP device available (this library has no CPU path)";
@@ -770,7 +778,55 @@ lm_status lm_index_build_synthetic(const lm_synth_spec *spec, const lm_options *
         if (dbg) fprintf(stderr, "[lm] builder: partition sort %.0f ms; %lld seeds (%lld outliers), %.2f B/seed\n", now_ms() - tf,
                          (long long)ix->n_seeds, (long long)ix->n_seeds_outlier, (double)ix->seed_bytes / std::max<double>(1.0, (double)ix->n_seeds));
         ix->tmp.release();
-        ix->hbm_bytes = ix->seed_bytes + (int64_t)((uint64_t)(nlocal * sp.gbytes) + 64 + (uint64_t)M * 8 + pfx.size() * 4 + nlocal * 20);
+        // ---- residency: the set is built in HBM as ever; the genomes beyond the budget then move to pinned host memory and the
+        // device store shrinks to the rest (a set that does not fit the device DURING the build is out of reach of this form)
+        ix->res.genomes_device = nlocal;
+        ix->res.genome_bytes_device = nlocal * sp.gbytes;
+        {
+            const int64_t nb = (((int64_t)spec->genome_len + 3) >> 2);
+            int64_t budget = rq.budget;
+            if (rq.mode == LM_GENOMES_AUTO && budget == 0) {
+                size_t fr = 0, tot = 0;
+                HIPCHK(hipMemGetInfo(&fr, &tot));
+                budget = lm_res_auto_budget((int64_t)fr + nlocal * sp.gbytes, 0); // (the store itself is part of what it may take)
+            }
+            // the builder's device slots are sp.gbytes wide (a little more padding than the loader's) and the budget is counted in
+            // those: the first `keep` genomes stay, the rest go to the host - the planner lays out the host side only
+            const int64_t keep = rq.mode == LM_GENOMES_DEVICE ? nlocal
+                                 : rq.mode == LM_GENOMES_HOST ? 0
+                                                              : std::min<int64_t>(nlocal, budget / sp.gbytes);
+            if (keep < nlocal) {
+                ResidencyPlan plan = plan_residency(std::vector<int64_t>((size_t)(nlocal - keep), nb), LM_GENOMES_HOST, 0, LM_RES_SEGMENT_BYTES);
+                plan.place.insert(plan.place.begin(), (size_t)keep, GenomePlace()); // (the kept genomes: in the device store)
+                plan.genomes_device = keep;
+                plan.bytes_device = keep * sp.gbytes;
+                if (!lm_res_alloc_host(ix, plan, g_open_error)) {
+                    delete ix;
+                    return LM_ERR_NOMEM;
+                }
+                for (int64_t l = keep; l < nlocal; l++) { // (pinned destination: DMA at the link's rate, one copy per genome)
+                    const GenomePlace &pl = plan.place[(size_t)l];
+                    HIPCHK(hipMemcpyAsync(ix->g_host_segs[(size_t)pl.seg].p + pl.off, ix->d_gbits.p + l * sp.gbytes, (size_t)nb,
+                                          hipMemcpyDeviceToHost, ix->st));
+                    h.genomes[(size_t)l].bits_off = -1; // (not in the device store)
+                    goff[(size_t)l] = -1;
+                }
+                bsync(ix);
+                {   // the device store shrinks to the genomes that stay (same offsets: they are the first `keep` slots)
+                    DBuf<uint8_t> kept;
+                    kept.alloc_exact((size_t)(keep * sp.gbytes) + 64, true, ix->st);
+                    if (keep > 0) HIPCHK(hipMemcpyAsync(kept.p, ix->d_gbits.p, (size_t)(keep * sp.gbytes), hipMemcpyDeviceToDevice, ix->st));
+                    bsync(ix);
+                    ix->d_gbits.release();
+                    std::swap(ix->d_gbits.p, kept.p);
+                    std::swap(ix->d_gbits.cap, kept.cap);
+                }
+                copy_up(ix->d_g_off, goff);
+                bsync(ix);
+                ix->view.gbits = ix->d_gbits.p;
+            }
+        }
+        ix->hbm_bytes = ix->seed_bytes + (int64_t)((uint64_t)ix->res.genome_bytes_device + 64 + (uint64_t)M * 8 + pfx.size() * 4 + nlocal * 20);
         lm_set_scratch_budget(ix);
     } catch (const std::exception &e) {
         g_open_error = e.what();
@@ -790,7 +846,9 @@ lm_status lm_index_fetch(lm_index *ix, int64_t local_genome, int64_t start, int6
         HIPCHK(hipSetDevice(ix->device));
         DBuf<uint8_t> d;
         d.ensure((size_t)len + 1);
-        hipLaunchKernelGGL(k_fetch_bases, dim3(gridn(len)), dim3(256), 0, ix->st, ix->d_gbits.p + G.bits_off, start, len, d.p);
+        // (a host-resident genome is read where it lives: this kernel and k_stage_genome_bits are the two that may)
+        const uint8_t *gsrc = !ix->g_hptr.empty() && ix->g_hptr[(size_t)local_genome] ? ix->g_hptr[(size_t)local_genome] : ix->d_gbits.p + G.bits_off;
+        hipLaunchKernelGGL(k_fetch_bases, dim3(gridn(len)), dim3(256), 0, ix->st, gsrc, start, len, d.p);
         HIPCHK(hipMemcpyAsync(out, d.p, (size_t)len, hipMemcpyDeviceToHost, ix->st));
         bsync(ix);
     } catch (const std::exception &e) {

@@ -386,9 +386,11 @@ std::string load_index(const std::string &dir, int shard_rank, int shard_count, 
         // what the seed packer needs of the genomes, known before their batch files are read (load_index_genomes)
         out.n_local_genomes = 0;
         out.max_genome_len = 1;
+        out.local_genome_bases.clear();
         for (int64_t g = 0; g < g0 && (size_t)g < rec_len.size(); g++)
             if (out.g2local.empty() || out.g2local[(size_t)g] >= 0) {
                 out.n_local_genomes++;
+                out.local_genome_bases.push_back(rec_len[(size_t)g]);
                 out.max_genome_len = std::max<int64_t>(out.max_genome_len, rec_len[(size_t)g]);
             }
     }

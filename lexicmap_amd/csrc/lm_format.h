@@ -52,6 +52,7 @@ struct HostIndex {
     int shard_rank = 0, shard_count = 1;
     int64_t n_local_genomes = 0, max_genome_len = 1; // from the batch .idx files (before the batches themselves are read)
     size_t gbits_bound = 0;        // upper bound of the packed bytes (+ padding) of this shard's genomes
+    std::vector<int32_t> local_genome_bases; // bases of every genome of this shard, local order (from the .idx files: the placement plan)
     // Optional: where load_index_genomes puts the packed bases of a local genome instead of appending them to `gbits` (the
     // loader: straight from the read buffer to their place on the device).  A sink that returns false stops the load (status 2).
     std::function<uint8_t *(size_t bytes)> gbits_buffer; // the buffer a run of records is read into (the loader: pinned memory)

@@ -283,6 +283,7 @@ template <typename T> struct DBuf {
     ~DBuf() { release(); }
     size_t bytes() const { return cap * sizeof(T); }
     static constexpr size_t ARENA_MIN = (size_t)32 << 20; // smaller buffers stay plain grow-only allocations
+    bool arena_always = false;     // ... unless the buffer must count against the scratch budget whatever its size
     void ensure(size_t n) {
         if (n <= cap && p) return;
         if (p && arena) { // the block goes back while earlier launches of this thread may still read it
@@ -290,7 +291,7 @@ template <typename T> struct DBuf {
         }
         release();
         size_t want = std::max<size_t>(n + n / 8, 64);
-        if (phase && tls_arena && want * sizeof(T) >= ARENA_MIN) {
+        if (phase && tls_arena && (arena_always || want * sizeof(T) >= ARENA_MIN)) {
             p = (T *)tls_arena->alloc(want * sizeof(T));
             arena = tls_arena;
         } else {
@@ -389,6 +390,17 @@ struct lm_index;
 void lm_fill_gap_lut(lm_index *ix);
 void lm_set_scratch_budget(lm_index *ix);
 void lm_reserve_lane_slabs(lm_index *ix);
+// residency of the 2-bit genomes (lm_residency.h, DESIGN.md residency; defined in lm_pipeline.hip)
+struct lm_res_request {
+    int mode = 0;       // RES_GENOMES_*
+    int64_t budget = 0; // AUTO: device bytes the genome store may take; 0 = derive from the free device memory
+};
+// res (may be null) and the LM_GENOME_PLACEMENT / LM_GENOME_HBM_MB switches -> the request; LM_ERR_OPTION + text for a bad value
+lm_status lm_res_resolve(const lm_residency *res, lm_res_request &out, std::string &err);
+// AUTO with budget 0: what the store may take of `free_bytes` once `other_bytes` (the seed image, when it is not there yet) are set aside
+int64_t lm_res_auto_budget(int64_t free_bytes, int64_t other_bytes);
+// cuts the plan's pinned segments (zero-filled) and fills ix->g_hptr / ix->res; false + text when the host refuses (LM_ERR_NOMEM)
+bool lm_res_alloc_host(lm_index *ix, const lm::ResidencyPlan &plan, std::string &err);
 
 namespace lm {
 struct Work;
@@ -476,6 +488,20 @@ struct lm_index {
     int gap_lut_n = 0;
     DevIndexView view;
     int64_t hbm_bytes = 0;
+    // host-resident genomes: pinned segments, and per local genome the (device-visible) address of its first byte there -
+    // null for a genome of d_gbits; g_hptr is empty when every genome is on the device
+    struct HostSeg {
+        uint8_t *p = nullptr;
+        size_t bytes = 0;
+    };
+    std::vector<HostSeg> g_host_segs;
+    std::vector<const uint8_t *> g_hptr;
+    std::vector<const uint8_t *> g_hhost; // the same places as the host addresses them (lm_index_save)
+    lm_residency_info res = {0, 0, 0, 0, 0}; // (stage_bytes is filled in by lm_index_get_residency)
+    ~lm_index() {
+        for (auto &sg : g_host_segs)
+            if (sg.p) (void)hipHostFree(sg.p);
+    }
     // scratch
     LaneSlabs lane_slabs;    // the two fixed slabs the lane arenas work in (LM_ARENA_RESERVE_PCT of the scratch budget)
     ScratchArena arena[2];   // phase buffers of the searches on this handle, one arena per lane (destroyed after work / actx)

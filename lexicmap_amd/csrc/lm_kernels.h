@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "lm_algos.h"
+#include "lm_residency.h"
 
 namespace lm {
 
@@ -45,6 +46,21 @@ struct Task { // one lexichash chain of one (query, genome): the pseudo-alignmen
     int32_t nseeds, wlen;
     int64_t woff;
     uint64_t bg; // batch:17|genome:17 key of the genome
+};
+
+// Where a task's 2-bit bases are read from: base + off + (pos >> 2) holds base `pos` of the task's genome.  The genome store
+// (base = gbits, off = g_off[g]) or, for a host-resident genome, the chunk's staging buffer (off = staged offset - first
+// copied byte of the genome: a multiple of 16, possibly negative).  A null array means "all in the store".
+struct TaskSrc {
+    const uint8_t *base;
+    int64_t off;
+};
+// one window of a host-resident genome for k_stage_genome_bits: `copy` bytes (a multiple of 16) from src (pinned host
+// memory) to dst (device), both 16-byte aligned, then LM_STAGE_TAIL bytes of zeros
+struct StageCmd {
+    const uint8_t *src;
+    uint8_t *dst;
+    int32_t copy, pad;
 };
 
 struct HspIn { // extendMatch input (lib-index-search.go:2255,2522)
@@ -101,10 +117,12 @@ void launch_make_tasks(hipStream_t st, DevIndexView ix, const uint64_t *segA, co
                        int32_t *order_scratch, Task *tasks);
 void launch_task_wlen(hipStream_t st, const Task *tasks, int64_t ntasks, int32_t *wlen);
 void launch_task_set_woff(hipStream_t st, Task *tasks, int64_t ntasks, const int64_t *woff);
-void launch_extract_windows(hipStream_t st, DevIndexView ix, const Task *tasks, int64_t ntasks, const int32_t *only,
-                            uint8_t *wbuf);
-void launch_extract_windows_at(hipStream_t st, DevIndexView ix, const Task *tasks, const int32_t *idx, const int64_t *dest,
-                               int64_t n, uint8_t *wbuf);
+// src (here and in the pseudo-alignment launchers): per task, or null when every genome is in the device store
+void launch_extract_windows(hipStream_t st, DevIndexView ix, const Task *tasks, const TaskSrc *src, int64_t ntasks,
+                            const int32_t *only, uint8_t *wbuf);
+void launch_extract_windows_at(hipStream_t st, DevIndexView ix, const Task *tasks, const TaskSrc *src, const int32_t *idx,
+                               const int64_t *dest, int64_t n, uint8_t *wbuf);
+void launch_stage_genome_bits(hipStream_t st, const StageCmd *cmds, int64_t n);
 #define LM_TAB_BITS_MIN 12 /* bucket table over the leading bits of a query's sorted k-mers: 2^12 .. 2^20 buckets */
 #define LM_TAB_BITS_MAX 20
 void launch_build_cmp_tab(hipStream_t st, const uint64_t *keys_cmp, const int64_t *posoff, const int32_t *nvalid, int nq,
@@ -116,11 +134,11 @@ void launch_build_cmp_bits(hipStream_t st, const uint64_t *keys_cmp, const int64
 #define LM_PA_MAX_SEGS 8192 /* segments (each with its own counter) of the candidate list of k_pa_filter */
 #define LM_PA_RANGE_SEGS 16 /* segments per range of task groups (= wavefronts of a k_pa_filter workgroup) */
 #define LM_PA_GROUP 64 /* chain windows per k_pa_filter workgroup pass */
-void launch_pa_filter(hipStream_t st, DevIndexView ix, const Task *tasks, int64_t ntasks, const uint8_t *wbuf,
+void launch_pa_filter(hipStream_t st, DevIndexView ix, const Task *tasks, const TaskSrc *src, int64_t ntasks, const uint8_t *wbuf,
                       const int64_t *posoff, const int32_t *nvalid, const uint32_t *cmp_bits, const int64_t *bits_off,
                       const int32_t *bits_log, int K, int min_prefix, unsigned long long *seg_count, int nseg, int64_t seg_cap,
                       uint64_t *cand, unsigned long long *group_counter, int ncu, int seg_by_group, bool roll = true);
-void launch_pa_search(hipStream_t st, DevIndexView ix, const Task *tasks, const uint8_t *wbuf, const uint64_t *keys_cmp,
+void launch_pa_search(hipStream_t st, DevIndexView ix, const Task *tasks, const TaskSrc *src, const uint8_t *wbuf, const uint64_t *keys_cmp,
                       const uint32_t *vals_cmp, const int64_t *posoff, const int32_t *nvalid, const uint32_t *cmp_tab,
                       const int64_t *tab_off, const int32_t *tab_bits, int K, int min_prefix,
                       const unsigned long long *seg_count, int nseg, int64_t seg_cap, const uint64_t *cand,

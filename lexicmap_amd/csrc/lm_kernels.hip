@@ -910,13 +910,14 @@ __global__ void k_task_set_woff(Task *__restrict__ tasks, int64_t ntasks, const 
 // genome.SubSeq3 (genome.go:931-1143) + RC (:2943) — one workgroup per chain window
 // `only` (may be null): per task, > 0 when its window is needed (tasks with pseudo-alignment results: extendMatch and WFA
 // read the ASCII window, the pseudo-alignment itself takes its k-mers from the packed genome)
-__global__ void k_extract_windows(DevIndexView ix, const Task *__restrict__ tasks, int64_t ntasks,
-                                  const int32_t *__restrict__ only, uint8_t *__restrict__ wbuf) {
+template <bool SRC>
+__global__ void k_extract_windows(DevIndexView ix, const Task *__restrict__ tasks, const TaskSrc *__restrict__ src,
+                                  int64_t ntasks, const int32_t *__restrict__ only, uint8_t *__restrict__ wbuf) {
     for (int64_t ti = blockIdx.x; ti < ntasks; ti += gridDim.x) {
         if (only && only[ti] <= 0) continue;
         const Task t = tasks[ti];
         if (t.wlen <= 0 || t.g < 0) continue;
-        const uint8_t *gb = ix.gbits + ix.g_off[t.g];
+        const uint8_t *gb = SRC ? src[ti].base + src[ti].off : ix.gbits + ix.g_off[t.g];
         uint8_t *w = wbuf + t.woff;
         for (int i = threadIdx.x; i < t.wlen; i += blockDim.x) {
             int pos = t.rc ? (t.tBegin + t.wlen - 1 - i) : (t.tBegin + i);
@@ -929,18 +930,41 @@ __global__ void k_extract_windows(DevIndexView ix, const Task *__restrict__ task
 
 // the same for a list of tasks, each window written at its own offset of a compact buffer (the windows of the tasks that
 // produced pseudo-alignment chains, gathered over several chunks for one extendMatch / WFA round)
-__global__ void k_extract_windows_at(DevIndexView ix, const Task *__restrict__ tasks, const int32_t *__restrict__ idx,
-                                     const int64_t *__restrict__ dest, int64_t n, uint8_t *__restrict__ wbuf) {
+template <bool SRC>
+__global__ void k_extract_windows_at(DevIndexView ix, const Task *__restrict__ tasks, const TaskSrc *__restrict__ src,
+                                     const int32_t *__restrict__ idx, const int64_t *__restrict__ dest, int64_t n,
+                                     uint8_t *__restrict__ wbuf) {
     for (int64_t li = blockIdx.x; li < n; li += gridDim.x) {
         const Task t = tasks[idx[li]];
         if (t.wlen <= 0 || t.g < 0) continue;
-        const uint8_t *gb = ix.gbits + ix.g_off[t.g];
+        const uint8_t *gb = SRC ? src[idx[li]].base + src[idx[li]].off : ix.gbits + ix.g_off[t.g];
         uint8_t *w = wbuf + dest[li];
         for (int i = threadIdx.x; i < t.wlen; i += blockDim.x) {
             int pos = t.rc ? (t.tBegin + t.wlen - 1 - i) : (t.tBegin + i);
             uint32_t code = (gb[pos >> 2] >> ((3 - (pos & 3)) << 1)) & 3u;
             if (t.rc) code = 3u - code;
             w[i] = (uint8_t)("ACGT"[code]);
+        }
+    }
+}
+
+// Host-resident genomes (DESIGN.md residency): the 2-bit byte range of one chain window, copied from pinned host memory
+// into the chunk's compact device staging buffer - one workgroup per window.  A lane loads 16 bytes, consecutive lanes
+// consecutive addresses (a wavefront asks the host link for 1 KB in one instruction, the workgroup keeps 4 KB per round in
+// flight; src and dst are multiples of 16), and stores them the same way; the LM_STAGE_TAIL bytes behind the copy are
+// zeroed.  This kernel and k_fetch_bases are the only ones that dereference host memory: the k-mer cutters of the
+// pseudo-alignment read 8 .. 20 unaligned bytes per lane, one small transaction each over the link.
+__global__ __launch_bounds__(256) void k_stage_genome_bits(const StageCmd *__restrict__ cmds, int64_t n) {
+    for (int64_t ci = blockIdx.x; ci < n; ci += gridDim.x) {
+        const StageCmd c = cmds[ci];
+        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+        const u32x4 *s = (const u32x4 *)c.src;
+        u32x4 *d = (u32x4 *)c.dst;
+        const int nv = c.copy >> 4, nt = nv + (LM_STAGE_TAIL >> 4);
+        for (int i = threadIdx.x; i < nt; i += blockDim.x) {
+            u32x4 v = {0u, 0u, 0u, 0u};
+            if (i < nv) v = __builtin_nontemporal_load(s + i); // read once: nothing of it belongs in the caches
+            d[i] = v;
         }
     }
 }
@@ -1069,8 +1093,12 @@ __device__ __forceinline__ bool pa_partial_rule(bool q, bool c, uint32_t f, int 
     }
     return r;
 }
-template <bool ROLL>
-__global__ __launch_bounds__(PA_THREADS) void k_pa_filter(DevIndexView ix, const Task *__restrict__ tasks, int64_t ntasks,
+// SRC: the tasks read their 2-bit bases through per-task sources (TaskSrc: a handle with host-resident genomes).  SRC = false is
+// the kernel of a handle with every genome in the device store: ix.gbits + g_off[g], the code it always was (the source
+// array costs that instantiation nothing - no argument is read, no register held, no LDS).
+template <bool ROLL, bool SRC>
+__global__ __launch_bounds__(PA_THREADS) void k_pa_filter(DevIndexView ix, const Task *__restrict__ tasks,
+                                                           const TaskSrc *__restrict__ src, int64_t ntasks,
                                                            const uint8_t *__restrict__ wbuf,
                                                            const int64_t *__restrict__ posoff,
                                                            const int32_t *__restrict__ nvalid,
@@ -1152,6 +1180,7 @@ __global__ __launch_bounds__(PA_THREADS) void k_pa_filter(DevIndexView ix, const
     __shared__ int32_t s_q[PA_GROUP], s_rc[PA_GROUP], s_tb[PA_GROUP], s_wlen[PA_GROUP], s_npos[PA_GROUP], s_log[PA_GROUP];
     __shared__ int32_t s_first[PA_GROUP + 1]; // first slice of every task of the current run of one query
     __shared__ int64_t s_goff[PA_GROUP], s_bits[PA_GROUP], s_woff[PA_GROUP];
+    __shared__ const uint8_t *s_gb[SRC ? PA_GROUP : 1]; // SRC: the task's base pointer (the device store or the chunk's staging buffer)
     __shared__ int s_next;
     // persistent workgroups (one per CU: the 140 KB of LDS allow no second one) that take the groups from a global counter:
     // a workgroup per group left the CUs empty most of the time, between the end of one 16-wavefront workgroup and the
@@ -1183,7 +1212,12 @@ __global__ __launch_bounds__(PA_THREADS) void k_pa_filter(DevIndexView ix, const
             s_tb[tid] = t.tBegin;
             s_wlen[tid] = t.wlen;
             s_npos[tid] = n > 0 && t.wlen - K + 1 > 0 ? t.wlen - K + 1 : 0;
-            s_goff[tid] = t.g >= 0 ? ix.g_off[t.g] : -1;
+            if constexpr (SRC) { // (a staged window's offset may be negative: the base pointer says "has a packed genome")
+                s_gb[tid] = t.g >= 0 ? src[t0g + tid].base : nullptr;
+                s_goff[tid] = t.g >= 0 ? src[t0g + tid].off : 0;
+            } else {
+                s_goff[tid] = t.g >= 0 ? ix.g_off[t.g] : -1;
+            }
             s_woff[tid] = t.woff;
             s_bits[tid] = cmp_bits ? bits_off[t.q] : -1;
             s_log[tid] = cmp_bits ? bits_log[t.q] : 0;
@@ -1236,7 +1270,9 @@ __global__ __launch_bounds__(PA_THREADS) void k_pa_filter(DevIndexView ix, const
                 const int slice = ROLL ? (npos + (s_first[j + 1] - s_first[j]) - 1) / (s_first[j + 1] - s_first[j]) : PA_SLICE;
                 const int p0 = (sl - s_first[j]) * slice, p1 = p0 + slice < npos ? p0 + slice : npos;
                 const int64_t goff = s_goff[j];
-                const uint8_t *gb = goff >= 0 ? ix.gbits : nullptr;
+                const uint8_t *gb;
+                if constexpr (SRC) gb = s_gb[j];
+                else gb = goff >= 0 ? ix.gbits : nullptr;
                 const uint8_t *w = wbuf + s_woff[j];
                 const int m = pa_min_prefix(min_prefix, t.wlen);
                 const int p = m > K ? K : m;
@@ -1415,7 +1451,9 @@ __global__ __launch_bounds__(PA_THREADS) void k_pa_filter(DevIndexView ix, const
 }
 
 #define PAS_STAGE 512 /* anchors a wavefront of k_pa_search stages in LDS between two appends to the global list */
+template <bool SRC> // (as k_pa_filter: per-task sources only in the instantiation a handle with host-resident genomes runs)
 __global__ __launch_bounds__(256) void k_pa_search(DevIndexView ix, const Task *__restrict__ tasks,
+                                                    const TaskSrc *__restrict__ src,
                                                     const uint8_t *__restrict__ wbuf,
                                                     const uint64_t *__restrict__ keys_cmp,
                                                     const uint32_t *__restrict__ vals_cmp,
@@ -1488,8 +1526,8 @@ __global__ __launch_bounds__(256) void k_pa_search(DevIndexView ix, const Task *
             i = (int)((uint32_t)rec >> 1);
             rcs = (rec & 1ull) != 0;
             const Task t = tasks[ti];
-            const uint8_t *gb = t.g >= 0 ? ix.gbits : nullptr;
-            const int64_t goff = t.g >= 0 ? ix.g_off[t.g] : 0;
+            const uint8_t *gb = t.g >= 0 ? (SRC ? src[ti].base : ix.gbits) : nullptr;
+            const int64_t goff = t.g >= 0 ? (SRC ? src[ti].off : ix.g_off[t.g]) : 0;
             uint64_t kmer, rc;
             pa_kmer(t, wbuf + t.woff, gb, goff, i, K, &kmer, &rc);
             key = rcs ? rc : kmer;
@@ -2614,16 +2652,20 @@ void launch_task_wlen(hipStream_t st, const Task *tasks, int64_t ntasks, int32_t
 void launch_task_set_woff(hipStream_t st, Task *tasks, int64_t ntasks, const int64_t *woff) {
     LM_LAUNCH_1D(k_task_set_woff, ntasks, st, tasks, ntasks, woff);
 }
-void launch_extract_windows(hipStream_t st, DevIndexView ix, const Task *tasks, int64_t ntasks, const int32_t *only,
-                            uint8_t *wbuf) {
+void launch_extract_windows(hipStream_t st, DevIndexView ix, const Task *tasks, const TaskSrc *src, int64_t ntasks,
+                            const int32_t *only, uint8_t *wbuf) {
     int g = (int)(ntasks < 1 ? 1 : (ntasks > 1048576 ? 1048576 : ntasks));
-    hipLaunchKernelGGL(k_extract_windows, dim3(g), dim3(256), 0, st, ix, tasks, ntasks, only, wbuf);
+    hipLaunchKernelGGL(src ? k_extract_windows<true> : k_extract_windows<false>, dim3(g), dim3(256), 0, st, ix, tasks, src, ntasks, only, wbuf);
 }
-void launch_extract_windows_at(hipStream_t st, DevIndexView ix, const Task *tasks, const int32_t *idx, const int64_t *dest,
-                               int64_t n, uint8_t *wbuf) {
+void launch_extract_windows_at(hipStream_t st, DevIndexView ix, const Task *tasks, const TaskSrc *src, const int32_t *idx,
+                               const int64_t *dest, int64_t n, uint8_t *wbuf) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(k_extract_windows_at, dim3((unsigned)std::min<int64_t>(n, 65536)), dim3(256), 0, st, ix, tasks, idx, dest, n,
-                       wbuf);
+    hipLaunchKernelGGL(src ? k_extract_windows_at<true> : k_extract_windows_at<false>, dim3((unsigned)std::min<int64_t>(n, 65536)), dim3(256), 0, st, ix, tasks, src, idx, dest,
+                       n, wbuf);
+}
+void launch_stage_genome_bits(hipStream_t st, const StageCmd *cmds, int64_t n) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_stage_genome_bits, dim3((unsigned)std::min<int64_t>(n, 65536)), dim3(256), 0, st, cmds, n);
 }
 void launch_build_cmp_tab(hipStream_t st, const uint64_t *keys_cmp, const int64_t *posoff, const int32_t *nvalid, int nq,
                           int K, const int64_t *tab_off, const int32_t *tab_bits, int64_t tab_words, uint32_t *tab) {
@@ -2639,7 +2681,7 @@ void launch_build_cmp_bits(hipStream_t st, const uint64_t *keys_cmp, const int64
     int g = nq < 1 ? 1 : (nq > 65536 ? 65536 : nq);
     hipLaunchKernelGGL(k_build_cmp_bits, dim3(g), dim3(256), 0, st, keys_cmp, posoff, nvalid, nq, K, bits_off, bits_log, bits);
 }
-void launch_pa_filter(hipStream_t st, DevIndexView ix, const Task *tasks, int64_t ntasks, const uint8_t *wbuf,
+void launch_pa_filter(hipStream_t st, DevIndexView ix, const Task *tasks, const TaskSrc *src, int64_t ntasks, const uint8_t *wbuf,
                       const int64_t *posoff, const int32_t *nvalid, const uint32_t *cmp_bits, const int64_t *bits_off,
                       const int32_t *bits_log, int K, int min_prefix, unsigned long long *seg_count, int nseg, int64_t seg_cap,
                       uint64_t *cand, unsigned long long *group_counter, int ncu, int seg_by_group, bool roll) {
@@ -2647,19 +2689,22 @@ void launch_pa_filter(hipStream_t st, DevIndexView ix, const Task *tasks, int64_
     int g = (int)(ngroups < 1 ? 1 : (ngroups > ncu ? ncu : ngroups));
     static bool lds_set = false;
     if (!lds_set) {
-        (void)hipFuncSetAttribute((const void *)k_pa_filter<true>, hipFuncAttributeMaxDynamicSharedMemorySize, PA_LDS_BYTES);
-        (void)hipFuncSetAttribute((const void *)k_pa_filter<false>, hipFuncAttributeMaxDynamicSharedMemorySize, PA_LDS_BYTES);
+        (void)hipFuncSetAttribute((const void *)k_pa_filter<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, PA_LDS_BYTES);
+        (void)hipFuncSetAttribute((const void *)k_pa_filter<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, PA_LDS_BYTES);
+        (void)hipFuncSetAttribute((const void *)k_pa_filter<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PA_LDS_BYTES);
+        (void)hipFuncSetAttribute((const void *)k_pa_filter<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PA_LDS_BYTES);
         lds_set = true;
     }
     // ROLL slices a window into pieces of up to PA_SLICE_ROLL = 2048 positions and takes its rolling branch only for K == 31; any
     // other k would fall into the strided branch, whose one-load-per-lane word cache covers 64 x 32 bases = PA_SLICE positions only
     // (the end of a 2048-position slice came out garbled and candidates were dropped): other k run the strided instantiation
     roll = roll && K == 31;
-    hipLaunchKernelGGL(roll ? k_pa_filter<true> : k_pa_filter<false>, dim3(g), dim3(PA_THREADS), PA_LDS_BYTES, st, ix, tasks, ntasks, wbuf,
+    auto kern = src ? (roll ? k_pa_filter<true, true> : k_pa_filter<false, true>) : (roll ? k_pa_filter<true, false> : k_pa_filter<false, false>);
+    hipLaunchKernelGGL(kern, dim3(g), dim3(PA_THREADS), PA_LDS_BYTES, st, ix, tasks, src, ntasks, wbuf,
                        posoff, nvalid, cmp_bits, bits_off, bits_log, K, min_prefix, seg_count, nseg, seg_cap, cand, group_counter,
                        seg_by_group);
 }
-void launch_pa_search(hipStream_t st, DevIndexView ix, const Task *tasks, const uint8_t *wbuf, const uint64_t *keys_cmp,
+void launch_pa_search(hipStream_t st, DevIndexView ix, const Task *tasks, const TaskSrc *src, const uint8_t *wbuf, const uint64_t *keys_cmp,
                       const uint32_t *vals_cmp, const int64_t *posoff, const int32_t *nvalid, const uint32_t *cmp_tab,
                       const int64_t *tab_off, const int32_t *tab_bits, int K, int min_prefix,
                       const unsigned long long *seg_count, int nseg, int64_t seg_cap, const uint64_t *cand,
@@ -2676,7 +2721,7 @@ void launch_pa_search(hipStream_t st, DevIndexView ix, const Task *tasks, const 
     static unsigned long long *d_dbg = nullptr;
     if (ps_dbg && !d_dbg && hipMalloc((void **)&d_dbg, 8 * sizeof(unsigned long long)) != hipSuccess) d_dbg = nullptr;
     if (ps_dbg && d_dbg) (void)hipMemsetAsync(d_dbg, 0, 8 * sizeof(unsigned long long), st);
-    hipLaunchKernelGGL(k_pa_search, dim3(nseg8 * bps), dim3(256), 0, st, ix, tasks, wbuf, keys_cmp, vals_cmp, posoff, nvalid, cmp_tab,
+    hipLaunchKernelGGL(src ? k_pa_search<true> : k_pa_search<false>, dim3(nseg8 * bps), dim3(256), 0, st, ix, tasks, src, wbuf, keys_cmp, vals_cmp, posoff, nvalid, cmp_tab,
                        tab_off, tab_bits, K, min_prefix, seg_count, seg_cap, bps, cand, count, cap, outA, outB, qbits, tbits, nseg,
                        xcd_map, ps_dbg ? d_dbg : nullptr);
     if (ps_dbg && d_dbg) {

@@ -186,6 +186,91 @@ void lm_set_scratch_budget(lm_index *ix) {
         if (getenv("LM_DEBUG")) fprintf(stderr, "[lm] the lane slabs were cut in %.0f ms (part of opening a production-size index)\n", lm::now_ms() - t0);
     }
 }
+// ---- residency of the 2-bit genomes (lm_residency.h) ----
+lm_status lm_res_resolve(const lm_residency *res, lm_res_request &out, std::string &err) {
+    out = lm_res_request();
+    if (res) { // an explicit request wins over the environment
+        if (res->genomes != LM_GENOMES_AUTO && res->genomes != LM_GENOMES_DEVICE && res->genomes != LM_GENOMES_HOST) {
+            err = "lm_residency.genomes must be LM_GENOMES_AUTO, LM_GENOMES_DEVICE or LM_GENOMES_HOST (got " + std::to_string(res->genomes) + ")";
+            return LM_ERR_OPTION;
+        }
+        if (res->genome_hbm_bytes < 0) {
+            err = "lm_residency.genome_hbm_bytes must not be negative";
+            return LM_ERR_OPTION;
+        }
+        out.mode = res->genomes;
+        out.budget = res->genome_hbm_bytes;
+        return LM_OK;
+    }
+    if (const char *e = getenv("LM_GENOME_PLACEMENT")) { // measurement only, like the other LM_* switches
+        const std::string v = e;
+        if (v == "device") out.mode = LM_GENOMES_DEVICE;
+        else if (v == "host") out.mode = LM_GENOMES_HOST;
+        else if (v == "auto" || v.empty()) out.mode = LM_GENOMES_AUTO;
+        else {
+            err = "LM_GENOME_PLACEMENT must be auto, device or host (got " + v + ")";
+            return LM_ERR_OPTION;
+        }
+    }
+    // a byte budget for AUTO (DEVICE and HOST have none: the variable is ignored there).  A budget of 0 bytes means "derive it
+    // from the free memory", so 0 MB - or anything that is not a positive number - is refused instead of meaning either
+    if (const char *e = getenv("LM_GENOME_HBM_MB")) {
+        const long long mb = atoll(e);
+        if (mb <= 0) {
+            err = std::string("LM_GENOME_HBM_MB must be a positive number of megabytes (got ") + e + "); LM_GENOME_PLACEMENT=host puts every genome on the host";
+            return LM_ERR_OPTION;
+        }
+        if (out.mode == LM_GENOMES_AUTO) out.budget = (int64_t)mb << 20;
+    }
+    return LM_OK;
+}
+// AUTO without a byte budget.  The store may take what is free beside the seed image, minus a floor for the handle's
+// scratch budget (lm_set_scratch_budget takes 80 % of what is left; a search needs at least a chunk of pseudo-alignment
+// anchors and the WFA pools: 1/8 of the device, at most 16 GB) and the 3-GB reserve lm_guarded_malloc keeps for the runtime.
+int64_t lm_res_auto_budget(int64_t free_bytes, int64_t other_bytes) {
+    size_t fr = 0, tot = 0;
+    if (hipMemGetInfo(&fr, &tot) != hipSuccess) tot = (size_t)free_bytes;
+    int64_t floor_bytes = std::min<int64_t>((int64_t)(tot / 8), (int64_t)16 << 30);
+    if (const char *e = getenv("LM_SCRATCH_BUDGET_MB")) floor_bytes = std::max<int64_t>(64, atoll(e)) << 20;
+    return std::max<int64_t>(0, free_bytes - other_bytes - floor_bytes - ((int64_t)3 << 30));
+}
+bool lm_res_alloc_host(lm_index *ix, const lm::ResidencyPlan &plan, std::string &err) {
+    ix->res.genomes_device = plan.genomes_device;
+    ix->res.genomes_host = plan.genomes_host;
+    ix->res.genome_bytes_device = plan.bytes_device;
+    ix->res.genome_bytes_host = plan.bytes_host;
+    if (plan.genomes_host == 0) return true;
+    for (int64_t b : plan.seg_bytes) {
+        lm_index::HostSeg sg;
+        sg.bytes = (size_t)b;
+        // (hipHostMallocDefault: pinned, mapped into the device's address space - coherent reads over the host link, no paging)
+        if (hipHostMalloc((void **)&sg.p, sg.bytes, hipHostMallocDefault) != hipSuccess || !sg.p) {
+            (void)hipGetLastError();
+            err = "pinned host allocation of " + std::to_string(sg.bytes >> 20) + " MB for host-resident genomes failed (segment " +
+                  std::to_string(ix->g_host_segs.size()) + " of " + std::to_string(plan.seg_bytes.size()) + ", " +
+                  std::to_string(plan.bytes_host >> 20) + " MB in all)";
+            return false;
+        }
+        memset(sg.p, 0, sg.bytes); // the padding behind every genome
+        ix->g_host_segs.push_back(sg);
+    }
+    ix->g_hptr.assign(plan.place.size(), nullptr);
+    ix->g_hhost.assign(plan.place.size(), nullptr);
+    for (size_t g = 0; g < plan.place.size(); g++)
+        if (plan.place[g].seg >= 0) {
+            void *dp = nullptr;
+            uint8_t *hp = ix->g_host_segs[(size_t)plan.place[g].seg].p + plan.place[g].off;
+            if (hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess || !dp) {
+                (void)hipGetLastError();
+                err = "pinned host memory of the host-resident genomes is not visible to the device";
+                return false;
+            }
+            ix->g_hptr[g] = (const uint8_t *)dp;
+            ix->g_hhost[g] = hp;
+        }
+    return true;
+}
+
 void lm_reserve_lane_slabs(lm_index *ix) {
     if (ix->tune.arena_reserve_pct <= 0 || ix->lane_slabs.asked || ix->scratch_budget <= 0) return;
     int64_t want = ix->scratch_budget / 100 * ix->tune.arena_reserve_pct;
@@ -965,8 +1050,16 @@ static lm_status check_options(const lm_options &o, int k, int mask_prefix, int 
 
 void lm_index_close(lm_index *ix);
 lm_status lm_index_open(const char *dir, const lm_options *opt, int device, lm_index **out) {
+    return lm_index_open_ex(dir, opt, nullptr, device, out);
+}
+lm_status lm_index_open_ex(const char *dir, const lm_options *opt, const lm_residency *res, int device, lm_index **out) {
     *out = nullptr;
     g_open_error.clear();
+    lm_res_request rq;
+    {
+        const lm_status rs = lm_res_resolve(res, rq, g_open_error);
+        if (rs != LM_OK) return rs;
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
         g_open_error = "no HIP device available (this library has no CPU path)";
@@ -1010,7 +1103,37 @@ lm_status lm_index_open(const char *dir, const lm_options *opt, int device, lm_i
         // the device, on the reader's own stream: no host copy of the genome store and no buffer of a batch file's size (12.5 GB
         // at C2 size: cutting and faulting in 6-GB buffers, appending to the store and uploading it from pageable memory
         // afterwards was 8 s of a 9.7-s open once the seed passes took 4.3 s).
-        ix->d_gbits.alloc_exact(h.gbits_bound + 64, true, S(ix)); // zero-filled: the padding behind every genome
+        // Where every genome goes is planned from the lengths in the batch indexes, before the batches are read (lm_residency.h).
+        // The seed image does not exist yet - the genome reader runs beside the seed passes - so an AUTO budget of 0 sets the
+        // seed files' size aside for it twice over (the packed image is smaller than its files; the passes' sort scratch is not).
+        ResidencyPlan plan;
+        {
+            std::vector<int64_t> gbytes;
+            for (int32_t b : h.local_genome_bases) gbytes.push_back(((int64_t)b + 3) / 4);
+            int64_t budget = rq.budget;
+            if (rq.mode == LM_GENOMES_AUTO && budget == 0) {
+                int64_t seed_file_bytes = 0;
+                for (auto &f : h.seed_files) {
+                    struct stat sb;
+                    if (stat(f.c_str(), &sb) == 0) seed_file_bytes += (int64_t)sb.st_size;
+                }
+                size_t fr = 0, tot = 0;
+                HIPCHK(hipMemGetInfo(&fr, &tot));
+                budget = lm_res_auto_budget((int64_t)fr, 2 * seed_file_bytes);
+            }
+            plan = plan_residency(gbytes, rq.mode, budget, LM_RES_SEGMENT_BYTES);
+            if (!lm_res_alloc_host(ix, plan, g_open_error)) {
+                lm_index_close(ix);
+                return LM_ERR_NOMEM;
+            }
+            if (getenv("LM_DEBUG"))
+                fprintf(stderr, "[lm] loader: %lld genomes (%.2f GB) in the device store, %lld (%.2f GB) in %zu pinned host segments\n",
+                        (long long)plan.genomes_device, (double)plan.bytes_device / 1e9, (long long)plan.genomes_host,
+                        (double)plan.bytes_host / 1e9, plan.seg_bytes.size());
+        }
+        // (everything on the device: the store is cut from the bound of the batch indexes, exactly as before there was a choice)
+        const size_t dev_store = plan.genomes_host == 0 ? h.gbits_bound + 64 : (size_t)plan.bytes_device + 64;
+        ix->d_gbits.alloc_exact(dev_store, true, S(ix)); // zero-filled: the padding behind every genome
         sync(ix);
         if (getenv("LM_DEBUG")) fprintf(stderr, "[lm] loader: the genome store (%.1f GB, zero-filled) was allocated in %.0f ms\n", (double)h.gbits_bound / 1e9, now_ms() - t_g0);
         struct GenomeSink {
@@ -1019,6 +1142,7 @@ lm_status lm_index_open(const char *dir, const lm_options *opt, int device, lm_i
             size_t pinned_cap = 0;
             uint8_t *dst = nullptr;
             size_t cap = 0;
+            size_t next = 0; // local genome the next call of the sink brings (the reader hands them over in local order)
             ~GenomeSink() {
                 if (st) (void)hipStreamSynchronize(st);
                 if (pinned) (void)hipHostFree(pinned);
@@ -1026,7 +1150,7 @@ lm_status lm_index_open(const char *dir, const lm_options *opt, int device, lm_i
             }
         } gsink;
         gsink.dst = ix->d_gbits.p;
-        gsink.cap = h.gbits_bound + 64;
+        gsink.cap = dev_store;
         HIPCHK(hipStreamCreateWithFlags(&gsink.st, hipStreamNonBlocking));
         const int gdev = device;
         h.gbits_buffer = [&gsink, gdev](size_t bytes) -> uint8_t * {
@@ -1048,9 +1172,21 @@ lm_status lm_index_open(const char *dir, const lm_options *opt, int device, lm_i
             }
             return gsink.pinned;
         };
-        h.gbits_sink = [&gsink](const uint8_t *src, size_t nbytes, int64_t off) {
-            if (off < 0 || (size_t)off + nbytes + 16 > gsink.cap) return false;
-            return hipMemcpyAsync(gsink.dst + off, src, nbytes, hipMemcpyHostToDevice, gsink.st) == hipSuccess;
+        h.gbits_sink = [&gsink, &plan, ix](const uint8_t *src, size_t nbytes, int64_t off) {
+            const size_t g = gsink.next++;
+            if (plan.genomes_host == 0) { // (offsets as the reader counts them)
+                if (off < 0 || (size_t)off + nbytes + 16 > gsink.cap) return false;
+                return hipMemcpyAsync(gsink.dst + off, src, nbytes, hipMemcpyHostToDevice, gsink.st) == hipSuccess;
+            }
+            // a plan with host-resident genomes: the genome's place is the plan's, which was made from the batch indexes
+            if (g >= plan.place.size() || (int64_t)nbytes > ((int64_t)ix->host.local_genome_bases[g] + 3) / 4) return false;
+            const GenomePlace &pl = plan.place[g];
+            if (pl.seg < 0) {
+                if ((size_t)pl.off + nbytes + 16 > gsink.cap) return false;
+                return hipMemcpyAsync(gsink.dst + pl.off, src, nbytes, hipMemcpyHostToDevice, gsink.st) == hipSuccess;
+            }
+            memcpy(ix->g_host_segs[(size_t)pl.seg].p + pl.off, src, nbytes); // pinned to pinned, on the reader's thread
+            return true;
         };
         h.gbits_batch_end = [&gsink]() { (void)hipStreamSynchronize(gsink.st); }; // the buffer is read into again
         std::future<std::string> gfut = std::async(std::launch::async, [&]() { return load_index_genomes(dir, h, gstatus); });
@@ -1298,6 +1434,7 @@ lm_status lm_index_open(const char *dir, const lm_options *opt, int device, lm_i
         std::vector<int32_t> glen;
         std::vector<uint64_t> gbg;
         for (size_t i = 0; i < h.genomes.size(); i++) {
+            if (plan.genomes_host > 0) h.genomes[i].bits_off = plan.place[i].seg < 0 ? plan.place[i].off : -1; // (-1: not in the device store)
             goff.push_back(h.genomes[i].bits_off);
             glen.push_back(h.genomes[i].len);
             gbg.push_back(h.genomes[i].bg);
@@ -1311,7 +1448,8 @@ lm_status lm_index_open(const char *dir, const lm_options *opt, int device, lm_i
         v.gbits = ix->d_gbits.p;
         v.g_off = ix->d_g_off.p;
         v.g_len = ix->d_g_len.p;
-        ix->hbm_bytes = ix->seed_bytes + (int64_t)(h.masks.size() * 8 + pfx.size() * 4 + (size_t)h.gbits_total + 64 + goff.size() * 20 +
+        if (plan.genomes_host == 0) ix->res.genome_bytes_device = h.gbits_total; // (what the reader placed: the plan's sum, from the records themselves)
+        ix->hbm_bytes = ix->seed_bytes + (int64_t)(h.masks.size() * 8 + pfx.size() * 4 + (size_t)ix->res.genome_bytes_device + 64 + goff.size() * 20 +
                                                    h.batch_first.size() * 8);
         // the host copy of the packed genomes is no longer needed
         std::vector<uint8_t>().swap(h.gbits);
@@ -1596,6 +1734,15 @@ struct AlignCtx {
     DBuf<LmChain2> out, out_compact;
     DBuf<int64_t> res_off;
     DBuf<Task> tasks;
+    // host-resident genomes: the chunk's staged 2-bit ranges, the per-task sources that point into them (or into the genome
+    // store), and the copy list of k_stage_genome_bits.  They stay until this context takes its next chunk, i.e. until the
+    // consumer has extracted the chunk's windows (align_range frees the slot after that).
+    DBuf<uint8_t> gstage;
+    DBuf<TaskSrc> tsrc;
+    DBuf<StageCmd> stage_cmds;
+    std::vector<TaskSrc> tsrc_h;
+    std::vector<StageCmd> stage_cmds_h;
+    const TaskSrc *src_d = nullptr; // of the chunk in hand; null: every genome is in the device store
     DBuf<HspIn> hsp_in;
     DBuf<HspExt> hsp_ext;
     DBuf<int32_t> ext_cap, ext_wcap, ext_msi;
@@ -1631,12 +1778,13 @@ struct AlignCtx {
     } wide;
     AlignCtx() {
         for_each_phase([](auto &b) { b.phase = true; });
+        gstage.arena_always = true; // the staging buffer counts against the lane's scratch budget whatever its size
     }
     ~AlignCtx() {
     }
     template <class F> void for_each_phase(F f) {
         f(wlen); f(woff); f(wbuf); f(gwbuf); f(gw_idx); f(gw_dest); f(pa_off); f(A0); f(B0); f(A1); f(B1); f(subs);
-        f(marks); f(msi); f(stack); f(out_n); f(clr_n); f(out); f(out_compact); f(res_off); f(tasks); f(hsp_in);
+        f(marks); f(msi); f(stack); f(out_n); f(clr_n); f(out); f(out_compact); f(res_off); f(tasks); f(gstage); f(tsrc); f(stage_cmds); f(hsp_in);
         f(hsp_ext); f(ext_cap); f(ext_wcap); f(ext_msi); f(ext_off); f(ext_subs); f(ext_rows); f(ext_rstart);
         f(wfa_in); f(wfa_out);  f(ops_pool);
         f(wide.in); f(wide.out); f(wide.todo); f(wide.hdr); f(wide.arena); f(wide.ops); f(wide.tmp);
@@ -1657,6 +1805,15 @@ struct AlignCtx {
 };
 
 } // namespace lm
+lm_status lm_index_get_residency(const lm_index *ix, lm_residency_info *info) {
+    if (!ix || !info) return LM_ERR_ARG;
+    *info = ix->res;
+    info->stage_bytes = 0;
+    for (AlignCtx *const *set : {ix->actx, ix->actx1})
+        for (int i = 0; i < 3; i++)
+            if (set[i]) info->stage_bytes += (int64_t)set[i]->gstage.bytes();
+    return LM_OK;
+}
 void lm_free_align_ctx(lm_index *ix, int lane) { // lane < 0: both
     if (lane != 1)
         for (auto &c : ix->actx) {
@@ -1678,6 +1835,64 @@ struct HspMeta { // host-side view of one WFA problem
     HspIn in;
     HspExt ext;
 };
+
+// Host-resident genomes: the 2-bit byte ranges of the chunk's windows go to the context's staging buffer (taken from the lane's
+// scratch arena: a request the budget cannot take is a DeviceOOM like any other scratch), one workgroup of k_stage_genome_bits
+// per window, and every task gets its source - the staged range, or its genome's place in the device store.  Returns the
+// device array (null when the handle has no host-resident genome: the kernels then read ix.gbits + g_off as ever).
+static const TaskSrc *stage_host_windows(AlignCtx &a, TaskSpan ht) {
+    lm_index *ix = a.ix;
+    a.src_d = nullptr;
+    if (ix->g_hptr.empty()) return nullptr;
+    const size_t nt = ht.size();
+    std::vector<TaskSrc> &src = a.tsrc_h;
+    std::vector<StageCmd> &cmds = a.stage_cmds_h;
+    src.assign(nt, TaskSrc{nullptr, 0});
+    cmds.clear();
+    int64_t used = 0, copied = 0;
+    for (size_t i = 0; i < nt; i++) { // pass 1: offsets into the staging buffer (multiples of 16)
+        const Task &t = ht[i];
+        if (t.g < 0) continue;
+        const uint8_t *hp = ix->g_hptr[(size_t)t.g];
+        if (!hp) {
+            src[i] = TaskSrc{ix->d_gbits.p, ix->host.genomes[(size_t)t.g].bits_off};
+        } else if (t.wlen > 0) {
+            const StageRange r = stage_range(t.tBegin, t.wlen);
+            StageCmd c;
+            c.src = hp + r.first;
+            c.dst = nullptr;
+            c.copy = (int32_t)r.copy;
+            c.pad = 0;
+            cmds.push_back(c);
+            src[i].off = used - r.first; // (base: pass 2)
+            used += r.total();
+            copied += r.copy;
+        } else {
+            src[i] = TaskSrc{ix->d_gbits.p, 0}; // (an empty window is never read)
+        }
+    }
+    a.gstage.ensure((size_t)used + 64);
+    size_t ci = 0;
+    int64_t at = 0;
+    for (size_t i = 0; i < nt; i++) { // pass 2: addresses
+        const Task &t = ht[i];
+        if (t.g < 0 || !ix->g_hptr[(size_t)t.g] || t.wlen <= 0) continue;
+        src[i].base = a.gstage.p;
+        cmds[ci].dst = a.gstage.p + at;
+        at += cmds[ci].copy + LM_STAGE_TAIL;
+        ci++;
+    }
+    a.tsrc.ensure(nt);
+    HIPCHK(hipMemcpyAsync(a.tsrc.p, src.data(), nt * sizeof(TaskSrc), hipMemcpyHostToDevice, S(ix)));
+    if (!cmds.empty()) {
+        a.stage_cmds.ensure(cmds.size());
+        HIPCHK(hipMemcpyAsync(a.stage_cmds.p, cmds.data(), cmds.size() * sizeof(StageCmd), hipMemcpyHostToDevice, S(ix)));
+        Prof p(ix, "k_stage_genome_bits", copied); // bytes read over the host link
+        launch_stage_genome_bits(S(ix), a.stage_cmds.p, (int64_t)cmds.size());
+    }
+    a.src_d = a.tsrc.p;
+    return a.src_d;
+}
 
 // Runs pseudo-alignment for tasks[t0,t1) (host copy `ht`), returns per task the Chain2 results.
 // `ht`: host copy of the tasks; `dev_tasks` their device copy (null: upload `ht`); `base` = window offset of the first
@@ -1706,6 +1921,8 @@ static void run_pseudo(AlignCtx &a, TaskSpan ht, std::vector<int64_t> &res_off_h
         HIPCHK(hipMemcpyAsync(a.tasks.p, ht.p, sizeof(Task) * nt, hipMemcpyHostToDevice, S(ix)));
         tasks_d = a.tasks.p;
     }
+    // (caller-provided ASCII windows have no packed genome behind them)
+    const TaskSrc *src_d = own_windows ? (a.src_d = nullptr) : stage_host_windows(a, ht);
     a.stats->window_bases += W;
     // key layout: when task number + anchor fields fit 64 bits the anchors are single compact keys (keys-only sort)
     int abits = 1, qbits = 1, tbits = 1;
@@ -1761,13 +1978,13 @@ static void run_pseudo(AlignCtx &a, TaskSpan ht, std::vector<int64_t> &res_off_h
         HIPCHK(hipMemsetAsync(a.pa_count.p, 0, (size_t)(2 + nseg) * sizeof(unsigned long long), S(ix)));
         {
             Prof p(ix, "k_pa_filter", W);
-            launch_pa_filter(S(ix), ix->view, tasks_d, nt, a.wb, qb->d_posoff.p, a.w->nvalid.p, a.w->cmp_bits.p,
+            launch_pa_filter(S(ix), ix->view, tasks_d, src_d, nt, a.wb, qb->d_posoff.p, a.w->nvalid.p, a.w->cmp_bits.p,
                              qb->d_bits_off.p, qb->d_bits_log.p, ix->host.k, 11, a.pa_count.p + 2, nseg, seg_cap, a.B1.p,
                              a.pa_count.p + 1, device_cus(ix->device), by_group ? 1 : 0, ix->tune.pa_filter_roll != 0);
         }
         {
             Prof p(ix, "k_pa_search");
-            launch_pa_search(S(ix), ix->view, tasks_d, a.wb, a.w->k_cmp, a.w->v_cmp, qb->d_posoff.p, a.w->nvalid.p,
+            launch_pa_search(S(ix), ix->view, tasks_d, src_d, a.wb, a.w->k_cmp, a.w->v_cmp, qb->d_posoff.p, a.w->nvalid.p,
                              a.w->cmp_tab.p, qb->d_tab_off.p, qb->d_tab_bits.p, ix->host.k, 11, a.pa_count.p + 2, nseg, seg_cap,
                              a.B1.p, a.pa_count.p, a.pa_cap, a.A0.p, a.B0.p, compact ? qbits : 0, compact ? tbits : 0,
                              by_group ? 1 : 0);
@@ -2868,7 +3085,8 @@ static void align_range(lm_index *ix, lm_qbatch *qb, Work &w, AlignCtx &a, TaskS
                 HIPCHK(hipMemcpyAsync(a.gw_idx.p, widx.data(), widx.size() * sizeof(int32_t), hipMemcpyHostToDevice, S(ix)));
                 HIPCHK(hipMemcpyAsync(a.gw_dest.p, wdest.data(), wdest.size() * sizeof(int64_t), hipMemcpyHostToDevice, S(ix)));
                 Prof p(ix, "k_extract_windows", (gw_used - wdest[0]) * 5 / 4);
-                launch_extract_windows_at(S(ix), ix->view, w.tasks.p + tpos, a.gw_idx.p, a.gw_dest.p, (int64_t)widx.size(), gwb().p);
+                // (host-resident genomes: the chunk's staged ranges are still with the context that ran its pseudo-alignment)
+                launch_extract_windows_at(S(ix), ix->view, w.tasks.p + tpos, ctxs[pc.slot]->src_d, a.gw_idx.p, a.gw_dest.p, (int64_t)widx.size(), gwb().p);
                 sync(ix); // the host lists go out of scope
             }
             cur->genomes.reserve(cur->genomes.size() + (size_t)ns);

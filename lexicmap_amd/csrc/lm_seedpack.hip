@@ -708,7 +708,11 @@ extern "C" lm_status lm_index_save(lm_index *ix, const char *dir_c, int chunks) 
                     }
                     const size_t nb = ((size_t)g->len + 3) >> 2;
                     bits.resize(nb);
-                    HIPCHK(hipMemcpy(bits.data(), ix->d_gbits.p + g->bits_off, nb, hipMemcpyDeviceToHost));
+                    {
+                        const size_t l = (size_t)(g - ix->host.genomes.data());
+                        if (!ix->g_hhost.empty() && ix->g_hhost[l]) memcpy(bits.data(), ix->g_hhost[l], nb); // host-resident: read where it lives
+                        else HIPCHK(hipMemcpy(bits.data(), ix->d_gbits.p + g->bits_off, nb, hipMemcpyDeviceToHost));
+                    }
                     fg.be(nb, 4);
                     fg.be((uint64_t)g->len, 4);
                     fg.put(bits.data(), nb);
