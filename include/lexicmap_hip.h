@@ -83,7 +83,7 @@ void lm_options_default(lm_options *opt);
  * v0.6.0), genomes of at most 2^28 bases (the reference's own limit, lib-index-build.go:421-425). */
 lm_status lm_index_open(const char *dir, const lm_options *opt, int device, lm_index **out);
 /* Synthetic genome set + seed index generated directly in HBM (benchmark input; nothing in the reference corresponds to
- * it — index building is out of the hot-path scope).  Genome g belongs to family g % families; genomes >= families are
+ * it — an index of real genomes is built with lm_index_builder_* below).  Genome g belongs to family g % families; genomes >= families are
  * mutated copies (substitution rate U(0,max_div), indel shifts at a tenth of that) of the family ancestor.  Honors
  * opt->shard_rank/shard_count.  See lexicmap_amd/csrc/lm_builder.hip for what is exact and what is simplified. */
 typedef struct lm_synth_spec {
@@ -124,6 +124,46 @@ typedef struct lm_residency_info {
 lm_status lm_index_open_ex(const char *dir, const lm_options *opt, const lm_residency *res, int device, lm_index **out);
 lm_status lm_index_build_synthetic_ex(const lm_synth_spec *spec, const lm_options *opt, const lm_residency *res, int device, lm_index **out);
 lm_status lm_index_get_residency(const lm_index *idx, lm_residency_info *info);
+/* ---------------------------------------------------------------------------------------------------------
+ * Index building from caller-supplied genomes (what `lexicmap index` does after it has read its FASTA files,
+ * lib-index-build.go:880-1407, 1581-1678): an incremental builder - the host streams genomes, every call borrows its
+ * arguments only until it returns - whose finish() leaves a handle like lm_index_open's: search, lm_index_mask_seeds,
+ * lm_index_fetch, lm_index_save, the genome filter and residency work on it unchanged.
+ *   lm_index_builder_add: one input genome.  Its contigs are joined with contig_interval A's; a contig that would take the
+ *     concatenation past max_genome starts the next chunk (genome record) of the same genome (:1581-1658), and the chunk list
+ *     goes where genomes.chunks.bin goes.  Bases are 2-bit coded by genome/genome.go:1427-1444 (N and most ambiguity codes
+ *     become A).  Spacers and runs of >= 5 N are skip regions (lib-gaps.go:38-60): no seed overlaps them.  Record number n
+ *     (counted over all accepted records, on every shard) gets the key (n / genome_batch_size) << 17 | n % genome_batch_size.
+ *     LM_ERR_ARG, nothing added, builder still usable: no contig, a contig longer than max_genome ("skipping a big genome",
+ *     :1601-1610), a record shorter than k or of 2^28 bases or more.  With opt->shard_count > 1 every rank is shown every
+ *     genome and keeps those whose first record number % shard_count == shard_rank (the loader's rule).
+ *   lm_index_builder_finish: captures (LexicHash, with the masks-without-a-matching-prefix rule), seed-desert filling, reversed
+ *     seeds, packed seed image; `res` of _new is honoured as by lm_index_build_synthetic_ex.  The builder is consumed whether
+ *     finish succeeds or not; after a failure lm_last_error(NULL) has the text.  LM_ERR_ARG when nothing was added.
+ * Not done here (nor by the reference at this point): reading FASTA / gz files, soft-masking, --max-kmer-freq, merging
+ * several builds; k must be 31 and the mask set may have at most two masks per p-base prefix (masks <= 2 * 4^p). */
+typedef struct lm_build_opt {      /* lm_build_opt_default(): the defaults of `lexicmap index` (index.go:538-619) */
+    int32_t k;                     /* 31 (only 31 is accepted, as in lm_index_build_synthetic) */
+    int32_t masks;                 /* 20000; [4, 65535] with at most two masks per p-base prefix, p = max(1, floor(log4 masks)):
+                                    * 4..8, 16..32, 64..128, 256..512, 1024..2048, 4096..8192, 16384..32768; others: LM_ERR_ARG */
+    int64_t mask_seed;             /* 1 */
+    int32_t max_desert, seed_dist; /* 100, 50 */
+    int32_t contig_interval;       /* 1000 */
+    int32_t genome_batch_size;     /* 5000; [1, 2^17] */
+    int32_t max_genome;            /* 20000000; <= 0: 2^28 - 1 */
+} lm_build_opt;
+typedef struct lm_contig {
+    const char *id;
+    const uint8_t *seq;
+    uint32_t len;
+} lm_contig;
+typedef struct lm_index_builder lm_index_builder;
+void lm_build_opt_default(lm_build_opt *o);
+lm_status lm_index_builder_new(const lm_build_opt *bo, const lm_options *opt, const lm_residency *res, int device, lm_index_builder **out);
+lm_status lm_index_builder_add(lm_index_builder *b, const char *genome_id, const lm_contig *contigs, size_t ncontigs);
+lm_status lm_index_builder_finish(lm_index_builder *b, lm_index **out); /* consumes b on success and on failure */
+void lm_index_builder_free(lm_index_builder *b);                        /* abandon */
+const char *lm_index_builder_last_error(const lm_index_builder *b);
 /* bases [start, start+len) of local genome `local_genome` as ASCII (used to derive synthetic queries) */
 lm_status lm_index_fetch(lm_index *idx, int64_t local_genome, int64_t start, int64_t len, uint8_t *out);
 /* Writes the resident (unsharded) index to `dir`: info.toml, seeds/chunk_NNN.bin (+ .idx, kv/kv-data.go:126-602) in at most

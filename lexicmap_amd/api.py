@@ -88,6 +88,25 @@ class SynthSpec(C.Structure):
                 ("max_desert", C.c_int32), ("seed_dist", C.c_int32)]
 
 
+class BuildOpt(C.Structure):
+    """lm_build_opt: the settings of `lexicmap index` that Index.from_genomes honours (BuildOpt.default(): its defaults)"""
+    _fields_ = [("k", C.c_int32), ("masks", C.c_int32), ("mask_seed", C.c_int64), ("max_desert", C.c_int32),
+                ("seed_dist", C.c_int32), ("contig_interval", C.c_int32), ("genome_batch_size", C.c_int32),
+                ("max_genome", C.c_int32)]
+
+    @classmethod
+    def default(cls, **kw):
+        o = cls()
+        lib().lm_build_opt_default(C.byref(o))
+        for k, v in kw.items():
+            setattr(o, k, v)
+        return o
+
+
+class Contig(C.Structure):
+    _fields_ = [("id", C.c_char_p), ("seq", C.c_char_p), ("len", C.c_uint32)]
+
+
 GENOMES_AUTO, GENOMES_DEVICE, GENOMES_HOST = 0, 1, 2  # lm_residency.genomes
 
 
@@ -135,6 +154,15 @@ def lib():
     L.lm_index_build_synthetic_ex.argtypes = [C.POINTER(SynthSpec), C.POINTER(Options), C.POINTER(Residency), C.c_int,
                                               C.POINTER(vp)]
     L.lm_index_get_residency.argtypes = [vp, C.POINTER(ResidencyInfo)]
+    L.lm_build_opt_default.argtypes = [C.POINTER(BuildOpt)]
+    L.lm_build_opt_default.restype = None
+    L.lm_index_builder_new.argtypes = [C.POINTER(BuildOpt), C.POINTER(Options), C.POINTER(Residency), C.c_int, C.POINTER(vp)]
+    L.lm_index_builder_add.argtypes = [vp, C.c_char_p, C.POINTER(Contig), C.c_size_t]
+    L.lm_index_builder_finish.argtypes = [vp, C.POINTER(vp)]
+    L.lm_index_builder_free.argtypes = [vp]
+    L.lm_index_builder_free.restype = None
+    L.lm_index_builder_last_error.argtypes = [vp]
+    L.lm_index_builder_last_error.restype = C.c_char_p
     L.lm_index_close.argtypes = [vp]
     L.lm_index_get_info.argtypes = [vp, C.POINTER(IndexInfo)]
     L.lm_index_masks.argtypes = [vp]
@@ -266,6 +294,20 @@ class Index:
         if st != 0:
             raise RuntimeError("lm_index_build_synthetic failed (%d): %s" % (st, L.lm_last_error(None).decode()))
         return cls(None, opt, device, _handle=h)
+
+    @classmethod
+    def from_genomes(cls, genomes, build_opt=None, options=None, device=0, residency=None):
+        """index built on the GPU from caller-supplied genomes (lm_index_builder_*): genomes is a list of
+        (genome_id, [(contig_id, seq bytes), ...]); build_opt a BuildOpt (None: the defaults of `lexicmap index`); residency as
+        in __init__.  A genome the builder refuses (LM_ERR_ARG: a contig longer than max_genome, a record shorter than k)
+        raises ValueError with the builder's text; nothing of it is added."""
+        b = IndexBuilder(build_opt, options, device, residency)
+        try:
+            for gid, contigs in genomes:
+                b.add(gid, contigs)
+            return b.finish()
+        finally:
+            b.close()
 
     def residency(self):
         """lm_index_get_residency: genomes and 2-bit bytes on the device / in pinned host memory, staging bytes held"""
@@ -562,6 +604,65 @@ class Index:
         n = lib().lm_profile_get(self.h, C.byref(p))
         return [dict(name=p[i].name.decode(), launches=p[i].launches, total_ms=p[i].total_ms, bytes=p[i].bytes)
                 for i in range(n)]
+
+
+class IndexBuilder:
+    """lm_index_builder: genomes are added one at a time (the host may stream them), finish() returns the Index"""
+
+    def __init__(self, build_opt=None, options=None, device=0, residency=None):
+        L = lib()
+        self.opt = options or default_options()
+        self.bo = build_opt or BuildOpt.default()
+        self.device = device
+        h = C.c_void_p()
+        st = L.lm_index_builder_new(C.byref(self.bo), C.byref(self.opt), C.byref(residency) if residency is not None else None,
+                                    device, C.byref(h))
+        if st != 0:
+            e = RuntimeError("lm_index_builder_new failed (%d): %s" % (st, L.lm_last_error(None).decode()))
+            e.status = st
+            raise e
+        self.h = h
+
+    def last_error(self):
+        return lib().lm_index_builder_last_error(self.h).decode()
+
+    def try_add(self, genome_id, contigs):
+        """lm_index_builder_add: the status (0 = added; 7 = LM_ERR_ARG: refused, see last_error(), the builder stays usable)"""
+        n = len(contigs)
+        arr = (Contig * max(n, 1))()
+        keep = []
+        for i, (cid, seq) in enumerate(contigs):
+            s = bytes(seq)
+            keep.append(s)
+            arr[i].id = cid.encode() if isinstance(cid, str) else cid
+            arr[i].seq = s
+            arr[i].len = len(s)
+        gid = genome_id.encode() if isinstance(genome_id, str) else genome_id
+        return lib().lm_index_builder_add(self.h, gid, arr, n)
+
+    def add(self, genome_id, contigs):
+        st = self.try_add(genome_id, contigs)
+        if st == 7:
+            raise ValueError(self.last_error())
+        if st != 0:
+            raise RuntimeError("lm_index_builder_add failed (%d): %s" % (st, self.last_error()))
+
+    def finish(self):
+        """lm_index_builder_finish: the builder is consumed whether it succeeds or not"""
+        L = lib()
+        h = C.c_void_p()
+        bh, self.h = self.h, None
+        st = L.lm_index_builder_finish(bh, C.byref(h))
+        if st != 0:
+            e = RuntimeError("lm_index_builder_finish failed (%d): %s" % (st, L.lm_last_error(None).decode()))
+            e.status = st
+            raise e
+        return Index(None, self.opt, self.device, _handle=h)
+
+    def close(self):
+        if self.h:
+            lib().lm_index_builder_free(self.h)
+            self.h = None
 
 
 def format_rows(rows, ids, lens, flags=0, want_text=True):

@@ -1,8 +1,9 @@
-// lm_builder.hip — synthetic genome set + seed index generated directly in HBM (bench / large-scale test input).
+// lm_builder.hip — the seed index built on the GPU.  Two builders: the synthetic genome set + index generated directly in
+// HBM (bench / large-scale test input, first half of this file) and the builder for caller-supplied genomes
+// (lm_index_builder_*, second half).
 //
-// Index BUILDING is outside the hot-path scope; this exists because the benchmark configurations
-// (10k x 5 Mb genomes and up) cannot be built by any CPU tool on a fresh box within minutes, and nothing persists on
-// the GPU box.  What it produces has the same structure as a reference-built index (lib-index-build.go):
+// The synthetic builder exists because the benchmark configurations (10k x 5 Mb genomes and up) cannot be built by any CPU
+// tool on a fresh box within minutes, and nothing persists on the GPU box.  What it produces has the same structure as a reference-built index (lib-index-build.go):
 //   * genomes: procedural i.i.d. ACGT ancestors per family; members are substituted (rate U(0,max_div)) and
 //     indel-shifted copies; single contig; stored 2-bit MSB-first like genome/genome.go:1471-1508
 //   * normal seeds: EXACT LexicHash capture per genome — for every mask the argmin of mask^kmer over both strands, all
@@ -857,5 +858,977 @@ lm_status lm_index_fetch(lm_index *ix, int64_t local_genome, int64_t start, int6
     }
     return LM_OK;
 }
+
+} // extern "C"
+
+// =====================================================================================================================
+// Index from caller-supplied genomes (lm_index_builder_*, include/lexicmap_hip.h).  The synthetic builder
+// above stays as it is (the benchmark's input); what follows are its siblings for genome records of any length, with
+// several contigs and skip regions: geometry from tables (g_off / g_len / g_bg + a CSR of skip regions) instead of
+// SynthDev, and the one masking rule the synthetic set never needs - a mask no k-mer of the genome shares its p-base
+// prefix with captures the argmin over ALL k-mers (lexichash MaskKnownDistinctPrefixes(..., checkShorterPrefix = true),
+// lib-index-build.go:1028).  Planner (records, spacers, skip regions, keys, shards): lm_build_plan.h.
+#include "lm_build_plan.h"
+
+namespace lm {
+
+struct GenomeTab {
+    const int64_t *g_off;   // [nlocal] byte offset of the record in the store
+    const int32_t *g_len;   // [nlocal] bases
+    const uint64_t *g_bg;   // [nlocal] batch << 17 | index
+    const int32_t *reg_off; // [nlocal + 1] CSR of the skip regions of every record
+    const int32_t *reg_s, *reg_e; // inclusive, ascending, disjoint
+};
+
+// does the k-mer starting at pos overlap a skip region, i.e. is pos inside one of the intervals [s - K + 1, e]
+// (the masking's skip-region cursor and the desert filling's interval test: one predicate for ascending disjoint regions)
+__device__ __forceinline__ bool kmer_skipped(const int32_t *__restrict__ rs, const int32_t *__restrict__ re, int n, int pos, int K) {
+    if (n == 0) return false;
+    int lo = 0, hi = n; // first region that ends at or behind pos
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (re[mid] < pos) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < n && pos + K - 1 >= rs[lo];
+}
+
+// ASCII contigs of one record -> its 2-bit concatenation (contigs + spacers of A), MSB first; one lane per packed byte.
+// src_off: where contig c starts in `ascii`; dst_off: where it starts in the concatenation; every byte of the record is written
+__global__ void k_pack_record(const uint8_t *__restrict__ ascii, const int64_t *__restrict__ src_off, const int32_t *__restrict__ dst_off,
+                              const int32_t *__restrict__ clen, int nc, int32_t len, uint8_t *__restrict__ out) {
+    const int64_t nb = ((int64_t)len + 3) >> 2;
+    for (int64_t by = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; by < nb; by += (int64_t)gridDim.x * blockDim.x) {
+        uint32_t v = 0;
+        int lo = 0, hi = nc; // the last contig that starts at or before the byte's first base
+        const int32_t i0 = (int32_t)(by << 2);
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (dst_off[mid] <= i0) lo = mid;
+            else hi = mid;
+        }
+        int c = lo;
+        for (int j = 0; j < 4; j++) {
+            const int32_t i = i0 + j;
+            uint32_t b = 0;
+            if (i < len) {
+                while (c + 1 < nc && dst_off[c + 1] <= i) c++;
+                const int32_t r = i - dst_off[c];
+                if (r < clen[c]) b = build_base_code(ascii[src_off[c] + r]); // (else: inside the spacer behind contig c)
+            }
+            v = (v << 2) | b;
+        }
+        out[by] = (uint8_t)v;
+    }
+}
+
+// k_capture_lds for records described by tables.  LDS = true: the per-mask minima in LDS as above; false (more masks than a
+// CU's LDS holds): in ghash[block][M].  Phase 1: argmin over the k-mers sharing a mask's prefix, k-mers that overlap a skip
+// region left out.  Phase 1b, the missing-prefix rule: a mask whose minimum is still untouched takes the argmin over ALL
+// k-mers of both strands - one lane per such mask, the k-mers cut 64 at a time and passed round the wavefront; the lane also
+// counts the occurrences of its minimum and keeps the first.  A wavefront without such a mask skips the sweep, so a genome
+// in which every prefix occurs (5 Mb: 600 k-mers per prefix) pays one pass over the minima.  Phase 2 as above, plus the
+// captures of phase 1b from what their lanes kept (a k-mer that occurs more than once is looked up again).
+// miss_pos / miss_cnt: [block][M] scratch, (pos << 1 | strand) + 1 of the first occurrence (0: captured in phase 1 or not at
+// all) and the number of occurrences.
+// a minimum as every lane of the workgroup sees it after a barrier: in global memory (LDS = false) the atomics of phase 1 went
+// to L2, so the read must not be served from a line an earlier plain load left in the CU's vector cache
+template <bool LDS> __device__ __forceinline__ unsigned long long cap_min_load(const unsigned long long *p) {
+    if (LDS) return *p;
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+template <bool LDS>
+__global__ __launch_bounds__(1024) void k_capture_g(GenomeTab gt, MaskTab mt, const uint8_t *__restrict__ gbits, int64_t l0,
+                                                    const uint64_t *__restrict__ dbl_map, const uint32_t *__restrict__ dbl_cnt,
+                                                    unsigned long long *__restrict__ ghash, uint32_t *__restrict__ miss_pos,
+                                                    uint32_t *__restrict__ miss_cnt, uint16_t *__restrict__ s_mask,
+                                                    uint64_t *__restrict__ s_kmer, uint64_t *__restrict__ s_val,
+                                                    unsigned long long *__restrict__ counter, unsigned long long cap,
+                                                    uint64_t *__restrict__ pos_keys, unsigned long long *__restrict__ pos_counter,
+                                                    unsigned long long pos_cap, unsigned long long *__restrict__ clk) {
+    extern __shared__ unsigned long long lds_dyn[];
+    const int c = blockIdx.x;
+    const int nw = ((1 << (2 * mt.p)) + 63) >> 6;
+    const bool stamp = clk && blockIdx.x == 0 && threadIdx.x == 0; // LM_DEBUG: the phases of the chunk's first record (100-MHz clock)
+    if (stamp) clk[0] = wall_clock64();
+    unsigned long long *hs = LDS ? lds_dyn : ghash + (int64_t)c * mt.M;  // [M]
+    unsigned long long *bm = LDS ? lds_dyn + mt.M : lds_dyn;             // [nw]
+    uint32_t *bc = (uint32_t *)(bm + nw);                                // [nw]
+    uint32_t *mp = miss_pos + (int64_t)c * mt.M, *mc = miss_cnt + (int64_t)c * mt.M;
+    const int64_t l = l0 + c;
+    const uint8_t *gb = gbits + gt.g_off[l];
+    const int npos = gt.g_len[l] - mt.K + 1;
+    const int32_t *rs = gt.reg_s + gt.reg_off[l], *re = gt.reg_e + gt.reg_off[l];
+    const int nreg = gt.reg_off[l + 1] - gt.reg_off[l];
+    const int shift = (mt.K - mt.p) << 1;
+    const int lane = threadIdx.x & 63;
+    for (int i = threadIdx.x; i < mt.M; i += blockDim.x) hs[i] = ~0ull;
+    for (int i = threadIdx.x; i < nw; i += blockDim.x) {
+        bm[i] = dbl_map[i];
+        bc[i] = dbl_cnt[i];
+    }
+    __syncthreads();
+    for (int pos = threadIdx.x; pos < npos; pos += blockDim.x) {
+        if (kmer_skipped(rs, re, nreg, pos, mt.K)) continue;
+        const uint64_t fwd = packed_kmer(gb, pos, mt.K);
+        const uint64_t rc = lm_revcomp(fwd, mt.K);
+#pragma unroll
+        for (int s = 0; s < 2; s++) {
+            const uint64_t x = s ? rc : fwd;
+            const uint32_t pf = (uint32_t)(x >> shift);
+            const unsigned long long w = bm[pf >> 6];
+            const int j0 = (int)(pf + bc[pf >> 6] + (uint32_t)__popcll(w & ((1ull << (pf & 63)) - 1)));
+            const int nj = 1 + (int)((w >> (pf & 63)) & 1ull);
+            for (int j = j0; j < j0 + nj; j++) {
+                const unsigned long long h = mt.masks[j] ^ x;
+                if (h < hs[j]) atomicMin(&hs[j], h);
+            }
+        }
+    }
+    __syncthreads();
+    if (stamp) clk[1] = wall_clock64();
+    // ---- phase 1b: masks whose prefix does not occur in the record (every lane owns the masks threadIdx.x + i * blockDim.x:
+    // nobody else reads or writes their minima here)
+    for (int r0 = 0; r0 < mt.M; r0 += blockDim.x) {
+        const int j = r0 + threadIdx.x;
+        const bool miss = j < mt.M && cap_min_load<LDS>(&hs[j]) == ~0ull;
+        if (!__any(miss)) {
+            if (j < mt.M) mp[j] = 0;
+            continue;
+        }
+        const unsigned long long mk = miss ? mt.masks[j] : 0ull;
+        unsigned long long best = ~0ull;
+        uint32_t bcode = 0, cnt = 0;
+        for (int base = 0; base < npos; base += 64) {
+            const int pos = base + lane;
+            const bool valid = pos < npos && !kmer_skipped(rs, re, nreg, pos, mt.K);
+            uint64_t f = 0, r = 0;
+            if (valid) {
+                f = packed_kmer(gb, pos, mt.K);
+                r = lm_revcomp(f, mt.K);
+            }
+            unsigned long long vm = __ballot(valid);
+            while (vm) {
+                const int t = __builtin_amdgcn_readfirstlane(__ffsll((long long)vm) - 1);
+                vm &= vm - 1;
+                const uint64_t ff = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(f >> 32), t) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)f, t);
+                const uint64_t rr = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(r >> 32), t) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)r, t);
+                const uint32_t code = (uint32_t)(base + t) << 1;
+                unsigned long long h = mk ^ ff;
+                if (h < best) {
+                    best = h;
+                    bcode = code;
+                    cnt = 1;
+                } else if (h == best) cnt++;
+                h = mk ^ rr;
+                if (h < best) {
+                    best = h;
+                    bcode = code | 1u;
+                    cnt = 1;
+                } else if (h == best) cnt++;
+            }
+        }
+        if (j < mt.M) {
+            const bool got = miss && best != ~0ull;
+            mp[j] = got ? bcode + 1u : 0u;
+            mc[j] = got ? cnt : 0u;
+            if (got) hs[j] = best;
+        }
+    }
+    if (!LDS) __threadfence();
+    __syncthreads();
+    if (stamp) clk[2] = wall_clock64();
+    const uint64_t bg = gt.g_bg[l];
+    // ---- phase 2: count, reserve one range of the staging arrays for the record, write (k_capture_lds)
+    uint32_t *wsum = bc + nw; // [16] wave totals
+    __shared__ unsigned long long base_seed, base_pos;
+    uint32_t mine = 0;
+    for (int sweep = 0; sweep < 2; sweep++) {
+        unsigned long long o = 0, po = 0;
+        if (sweep == 1) {
+            uint32_t incl = mine;
+            const int wave = threadIdx.x >> 6;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const uint32_t v = __shfl_up(incl, d);
+                if (lane >= d) incl += v;
+            }
+            if (lane == 63) wsum[wave] = incl;
+            __syncthreads();
+            uint32_t before = 0, all = 0;
+            for (int w2 = 0; w2 < (int)(blockDim.x >> 6); w2++) {
+                if (w2 < wave) before += wsum[w2];
+                all += wsum[w2];
+            }
+            if (threadIdx.x == 0) {
+                base_seed = atomicAdd(counter, (unsigned long long)all);
+                base_pos = atomicAdd(pos_counter, (unsigned long long)all);
+            }
+            __syncthreads();
+            o = base_seed + before + (incl - mine);
+            po = base_pos + before + (incl - mine);
+        }
+        auto emit = [&](int j, uint64_t x, uint32_t code) { // code = pos << 1 | strand
+            if (o < cap) {
+                s_mask[o] = (uint16_t)j;
+                s_kmer[o] = x;
+                s_val[o] = (bg << 30) | ((uint64_t)(code >> 1) << 2) | ((uint64_t)(code & 1u) << 1);
+            }
+            if (po < pos_cap) pos_keys[po] = ((uint64_t)c << 32) | (uint64_t)code;
+            o++;
+            po++;
+        };
+        for (int pos = threadIdx.x; pos < npos; pos += blockDim.x) {
+            if (kmer_skipped(rs, re, nreg, pos, mt.K)) continue;
+            const uint64_t fwd = packed_kmer(gb, pos, mt.K);
+            const uint64_t rc = lm_revcomp(fwd, mt.K);
+#pragma unroll
+            for (int s = 0; s < 2; s++) {
+                const uint64_t x = s ? rc : fwd;
+                const uint32_t pf = (uint32_t)(x >> shift);
+                const unsigned long long w = bm[pf >> 6];
+                const int j0 = (int)(pf + bc[pf >> 6] + (uint32_t)__popcll(w & ((1ull << (pf & 63)) - 1)));
+                const int nj = 1 + (int)((w >> (pf & 63)) & 1ull);
+                for (int j = j0; j < j0 + nj; j++) {
+                    if ((mt.masks[j] ^ x) != cap_min_load<LDS>(&hs[j])) continue;
+                    if (x == 0 || lm_low_complexity(x, mt.K)) continue;
+                    if (sweep == 0) mine++;
+                    else emit(j, x, ((uint32_t)pos << 1) | (uint32_t)s);
+                }
+            }
+        }
+        // the captures of phase 1b (a k-mer reached here shares no prefix with its mask: the loop above never saw the pair)
+        for (int r0 = 0; r0 < mt.M; r0 += blockDim.x) {
+            const int j = r0 + threadIdx.x;
+            const uint32_t first = j < mt.M ? mp[j] : 0u;
+            const uint32_t cnt = first ? mc[j] : 0u;
+            const unsigned long long mk = first ? mt.masks[j] : 0ull, hj = first ? cap_min_load<LDS>(&hs[j]) : 0ull;
+            const uint64_t x = hj ^ mk;
+            const bool act = first != 0 && x != 0 && !lm_low_complexity(x, mt.K);
+            if (sweep == 0) {
+                if (act) mine += cnt;
+                continue;
+            }
+            if (act && cnt == 1) emit(j, x, first - 1u);
+            const bool multi = act && cnt > 1;
+            if (!__any(multi)) continue;
+            for (int base = 0; base < npos; base += 64) { // every occurrence of a k-mer that occurs more than once
+                const int pos = base + lane;
+                const bool valid = pos < npos && !kmer_skipped(rs, re, nreg, pos, mt.K);
+                uint64_t f = 0, r = 0;
+                if (valid) {
+                    f = packed_kmer(gb, pos, mt.K);
+                    r = lm_revcomp(f, mt.K);
+                }
+                unsigned long long vm = __ballot(valid);
+                while (vm) {
+                    const int t = __builtin_amdgcn_readfirstlane(__ffsll((long long)vm) - 1);
+                    vm &= vm - 1;
+                    const uint64_t ff = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(f >> 32), t) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)f, t);
+                    const uint64_t rr = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(r >> 32), t) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)r, t);
+                    const uint32_t code = (uint32_t)(base + t) << 1;
+                    if (multi && ff == x) emit(j, x, code);
+                    if (multi && rr == x) emit(j, x, code | 1u);
+                }
+            }
+        }
+    }
+    if (stamp) clk[3] = wall_clock64();
+}
+
+__global__ void k_pseudo_pos_g(GenomeTab gt, int64_t l0, int nchunk, int K, uint64_t *__restrict__ pos_keys, unsigned long long base) {
+    int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c < nchunk) pos_keys[base + c] = ((uint64_t)c << 32) | ((uint64_t)(uint32_t)(gt.g_len[l0 + c] - K) << 1) | 1ull; // sorts last
+}
+
+// k_desert_fill for records described by tables: the walk starts from pre = 0 and ends at the pseudo position len - K of THAT
+// record, the window is clipped to that record, and a candidate whose k-mer overlaps a skip region is passed over in the
+// upstream and in the downstream scan (add_one's in_intervals) - the window masking itself ignores skip regions
+// (MaskKnownDistinctPrefixes(window, nil, false), lib-index-build.go:1198).
+__global__ __launch_bounds__(256) void k_desert_fill_g(GenomeTab gt, MaskTab mt, const uint8_t *__restrict__ gbits, int64_t l0,
+                                                        const uint64_t *__restrict__ pos_keys, int64_t npk, int max_desert,
+                                                        int seed_dist, uint16_t *__restrict__ s_mask,
+                                                        uint64_t *__restrict__ s_kmer, uint64_t *__restrict__ s_val,
+                                                        unsigned long long *__restrict__ counter, unsigned long long cap) {
+    const int seed_pos_r = seed_dist / 2;
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t base = wave * 64; base < npk; base += nwaves * 64) {
+        const int64_t t = base + lane;
+        int c = 0, pos = 0, pre = 0;
+        bool isd = false;
+        if (t < npk) {
+            const uint64_t key = pos_keys[t];
+            c = (int)(key >> 32);
+            pos = (int)((key & 0xffffffffu) >> 1);
+            if (t > 0 && (int)(pos_keys[t - 1] >> 32) == c) pre = (int)((pos_keys[t - 1] & 0xffffffffu) >> 1);
+            isd = pos - pre >= max_desert;
+        }
+        uint64_t todo = __ballot(isd);
+        while (todo) {
+            const int src = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            const int gc = __builtin_amdgcn_readfirstlane(__shfl(c, src, 64));
+            const int gpos = __builtin_amdgcn_readfirstlane(__shfl(pos, src, 64));
+            const int gpre = __builtin_amdgcn_readfirstlane(__shfl(pre, src, 64));
+            const int64_t l = l0 + gc;
+            const uint8_t *gb = gbits + gt.g_off[l];
+            const int glen = gt.g_len[l];
+            const uint64_t bg = gt.g_bg[l];
+            const int32_t *rs = gt.reg_s + gt.reg_off[l], *re = gt.reg_e + gt.reg_off[l];
+            const int nreg = gt.reg_off[l + 1] - gt.reg_off[l];
+            int wstart = gpre - 1000;
+            if (wstart < 0) wstart = 0;
+            int wend = gpos + 1000 + mt.K;
+            if (wend > glen) wend = glen;
+            const int nk = wend - wstart - mt.K + 1; // k-mers of the window
+            auto try_at = [&](int at, uint64_t *kmer, int *strand, int *im) { // the candidate at record position `at`
+                const int rel = at - wstart;
+                if (rel < 0 || rel >= nk) return false;
+                if (kmer_skipped(rs, re, nreg, at, mt.K)) return false;
+                const uint64_t f = packed_kmer(gb, at, mt.K);
+                if (f != 0 && !lm_low_complexity(f, mt.K)) {
+                    const int m = desert_capturing_mask(mt, gb, wstart, nk, f, lane);
+                    if (m >= 0) {
+                        *kmer = f;
+                        *strand = 0;
+                        *im = m;
+                        return true;
+                    }
+                }
+                const uint64_t r = lm_revcomp(f, mt.K);
+                if (r != 0 && !lm_low_complexity(r, mt.K)) {
+                    const int m = desert_capturing_mask(mt, gb, wstart, nk, r, lane);
+                    if (m >= 0) {
+                        *kmer = r;
+                        *strand = 1;
+                        *im = m;
+                        return true;
+                    }
+                }
+                return false;
+            };
+            int j = gpre + seed_dist;
+            while (j < gpos) {
+                const int start_dn = j + 1, end_up = j - seed_pos_r;
+                bool ok = false;
+                uint64_t kmer = 0;
+                int strand = 0, im = -1, at = j;
+                for (; at > end_up; at--)
+                    if (try_at(at, &kmer, &strand, &im)) {
+                        ok = true;
+                        break;
+                    }
+                if (!ok) {
+                    if (start_dn >= gpos) break;
+                    int end_dn = start_dn + seed_pos_r;
+                    if (end_dn >= gpos) end_dn = gpos - 1;
+                    for (at = start_dn; at < end_dn; at++)
+                        if (try_at(at, &kmer, &strand, &im)) {
+                            ok = true;
+                            break;
+                        }
+                }
+                if (ok && lane == 0) {
+                    const unsigned long long o = atomicAdd(counter, 1ull);
+                    if (o < cap) {
+                        s_mask[o] = (uint16_t)im;
+                        s_kmer[o] = kmer;
+                        s_val[o] = (bg << 30) | ((uint64_t)at << 2) | ((uint64_t)strand << 1);
+                    }
+                }
+                j = at + seed_dist;
+            }
+        }
+    }
+}
+
+} // namespace lm
+
+struct lm_index_builder {
+    lm_build_opt bo;
+    lm_res_request rq;
+    lm_index *ix = nullptr;
+    std::string err;
+    bool broken = false;              // a device error left a genome half added
+    int64_t nrecords = 0, ninput = 0, input_bases = 0, max_len = 1;
+    int nlists = 0;
+    // the 2-bit store while it grows: device slabs laid out as consecutive pieces of the final store
+    struct Slab {
+        lm::DBuf<uint8_t> d;
+        int64_t first = 0, used = 0, cap = 0;
+    };
+    std::vector<std::unique_ptr<Slab>> slabs;
+    int64_t slab_bytes = (int64_t)256 << 20, store_bytes = 0;
+    int64_t stage_seeds = 0;          // > 0 (LM_BUILD_STAGE_SEEDS): first size of the seed staging arrays instead of the estimate
+    std::vector<int32_t> reg_off{0}, reg_s, reg_e; // skip regions of the local records (CSR)
+    std::vector<int32_t> g2local;                  // sharded: record number -> local number or -1
+    std::vector<int32_t> pfx;
+    lm::PBuf<uint8_t> stage;
+    lm::DBuf<uint8_t> d_ascii;
+    lm::DBuf<int64_t> d_src;
+    lm::DBuf<int32_t> d_dst, d_len;
+    ~lm_index_builder() {
+        if (ix) {
+            (void)hipSetDevice(ix->device);
+            if (ix->st) (void)hipStreamSynchronize(ix->st);
+        }
+        slabs.clear();
+        if (ix) lm_index_close(ix);
+    }
+};
+
+namespace lm {
+
+// packs one record into the growing store (its slot: build_slot_bytes, zero-padded); returns its byte offset in the final store
+static int64_t builder_pack(lm_index_builder *b, const BuildRecord &r, const lm_contig *contigs) {
+    lm_index *ix = b->ix;
+    const int64_t slot = build_slot_bytes(r.len);
+    if (b->slabs.empty() || b->slabs.back()->used + slot > b->slabs.back()->cap) {
+        std::unique_ptr<lm_index_builder::Slab> s(new lm_index_builder::Slab());
+        s->cap = std::max<int64_t>(b->slab_bytes, slot);
+        s->first = b->store_bytes;
+        s->d.alloc_exact((size_t)s->cap + 64, true, ix->st);
+        b->slabs.push_back(std::move(s));
+    }
+    lm_index_builder::Slab &sl = *b->slabs.back();
+    std::vector<int64_t> src((size_t)r.n);
+    std::vector<int32_t> len((size_t)r.n);
+    int64_t total = 0;
+    for (int c = 0; c < r.n; c++) {
+        src[(size_t)c] = total;
+        len[(size_t)c] = (int32_t)contigs[r.first + c].len;
+        total += contigs[r.first + c].len;
+    }
+    // (the caller's memory may move after the call: everything is staged in pinned memory and on the device before it returns)
+    b->stage.ensure((size_t)total + 64);
+    for (int c = 0; c < r.n; c++)
+        if (len[(size_t)c] > 0) memcpy(b->stage.p + src[(size_t)c], contigs[r.first + c].seq, (size_t)len[(size_t)c]);
+    b->d_ascii.ensure((size_t)total + 64);
+    b->d_src.ensure((size_t)r.n);
+    b->d_dst.ensure((size_t)r.n);
+    b->d_len.ensure((size_t)r.n);
+    if (total > 0) HIPCHK(hipMemcpyAsync(b->d_ascii.p, b->stage.p, (size_t)total, hipMemcpyHostToDevice, ix->st));
+    HIPCHK(hipMemcpyAsync(b->d_src.p, src.data(), (size_t)r.n * 8, hipMemcpyHostToDevice, ix->st));
+    HIPCHK(hipMemcpyAsync(b->d_dst.p, r.dst_off.data(), (size_t)r.n * 4, hipMemcpyHostToDevice, ix->st));
+    HIPCHK(hipMemcpyAsync(b->d_len.p, len.data(), (size_t)r.n * 4, hipMemcpyHostToDevice, ix->st));
+    // (a slab is zeroed when it is cut, but a genome that failed half way may have been here before: the padding must be zero)
+    HIPCHK(hipMemsetAsync(sl.d.p + sl.used, 0, (size_t)slot, ix->st));
+    hipLaunchKernelGGL(k_pack_record, dim3(gridn(((int64_t)r.len + 3) >> 2)), dim3(256), 0, ix->st, b->d_ascii.p, b->d_src.p, b->d_dst.p,
+                       b->d_len.p, r.n, r.len, sl.d.p + sl.used);
+    HIPCHK(hipGetLastError());
+    bsync(ix);
+    const int64_t off = sl.first + sl.used;
+    sl.used += slot;
+    b->store_bytes = off + slot;
+    return off;
+}
+
+static void builder_finish(lm_index_builder *b, const lm_res_request &rq) {
+    lm_index *ix = b->ix;
+    HostIndex &h = ix->host;
+    const lm_build_opt &bo = b->bo;
+    const int K = h.k, M = h.M, p = h.mask_prefix;
+    const int64_t nlocal = (int64_t)h.genomes.size();
+    const bool dbg = getenv("LM_DEBUG") != nullptr;
+    const double t0 = now_ms();
+    auto copy_up = [&](auto &dbuf, const auto &vec) {
+        dbuf.ensure(std::max<size_t>(vec.size(), 1));
+        if (!vec.empty()) HIPCHK(hipMemcpyAsync(dbuf.p, vec.data(), vec.size() * sizeof(vec[0]), hipMemcpyHostToDevice, ix->st));
+    };
+    // ---- the store: one allocation, the slabs copied to their places (they ARE consecutive pieces of it) and released
+    b->d_ascii.release();
+    ix->d_gbits.alloc_exact((size_t)b->store_bytes + 64, true, ix->st);
+    for (auto &s : b->slabs)
+        if (s->used > 0) HIPCHK(hipMemcpyAsync(ix->d_gbits.p + s->first, s->d.p, (size_t)s->used, hipMemcpyDeviceToDevice, ix->st));
+    bsync(ix);
+    b->slabs.clear();
+    // ---- tables
+    h.total_bases = ix->opt.total_bases_override > 0 ? ix->opt.total_bases_override : b->input_bases;
+    h.input_genomes = b->ninput;
+    h.genome_batch_size = bo.genome_batch_size;
+    h.rand_seed = bo.mask_seed;
+    h.max_seed_dist = bo.max_desert;
+    h.seed_dist_in_desert = bo.seed_dist;
+    h.genome_batches = (int)((b->nrecords + bo.genome_batch_size - 1) / bo.genome_batch_size);
+    h.batch_first.assign((size_t)h.genome_batches + 1, 0);
+    for (int i = 0; i <= h.genome_batches; i++) h.batch_first[(size_t)i] = std::min<int64_t>((int64_t)i * bo.genome_batch_size, b->nrecords);
+    h.n_local_genomes = nlocal;
+    h.max_genome_len = b->max_len;
+    h.has_chunks = !h.chunk_of.empty();
+    if (h.shard_count > 1) h.g2local = b->g2local;
+    std::vector<int64_t> goff((size_t)nlocal), slot((size_t)nlocal);
+    std::vector<int32_t> glen((size_t)nlocal);
+    std::vector<uint64_t> gbg((size_t)nlocal);
+    for (int64_t l = 0; l < nlocal; l++) {
+        const HostGenome &G = h.genomes[(size_t)l];
+        goff[(size_t)l] = G.bits_off;
+        glen[(size_t)l] = G.len;
+        gbg[(size_t)l] = G.bg;
+        slot[(size_t)l] = build_slot_bytes(G.len);
+        ix->bg2local[G.bg] = (int)l;
+    }
+    copy_up(ix->d_g_off, goff);
+    copy_up(ix->d_g_len, glen);
+    copy_up(ix->d_g_bg, gbg);
+    copy_up(ix->d_batch_first, h.batch_first);
+    if (!h.g2local.empty()) copy_up(ix->d_g2local, h.g2local);
+    DBuf<int32_t> d_reg_off, d_reg_s, d_reg_e;
+    copy_up(d_reg_off, b->reg_off);
+    copy_up(d_reg_s, b->reg_s);
+    copy_up(d_reg_e, b->reg_e);
+    lm_fill_gap_lut(ix);
+    bsync(ix);
+    DevIndexView &v = ix->view;
+    v.K = K;
+    v.M = M;
+    v.mask_prefix = p;
+    v.masks = ix->d_masks.p;
+    v.pfx_first = ix->d_pfx_first.p;
+    v.g_bg = ix->d_g_bg.p;
+    v.gbits = ix->d_gbits.p;
+    v.g_off = ix->d_g_off.p;
+    v.g_len = ix->d_g_len.p;
+    v.batch_first = ix->d_batch_first.p;
+    v.nbatches = h.genome_batches;
+    v.ngenomes = nlocal;
+    v.shard_rank = h.shard_rank;
+    v.shard_count = h.shard_count;
+    v.g2local = h.g2local.empty() ? nullptr : ix->d_g2local.p;
+    const MaskTab mt{ix->d_masks.p, ix->d_pfx_first.p, K, p, M};
+    const GenomeTab gt{ix->d_g_off.p, ix->d_g_len.p, ix->d_g_bg.p, d_reg_off.p, d_reg_s.p, d_reg_e.p};
+    // ---- prefix -> masks without a table in memory (k_capture_lds): every prefix once or twice (checked by _new)
+    const std::vector<int32_t> &pfx = b->pfx;
+    const int npfx = 1 << (2 * p), nwords = (npfx + 63) >> 6;
+    std::vector<uint64_t> dmap((size_t)nwords, 0);
+    std::vector<uint32_t> dcnt((size_t)nwords, 0);
+    for (int f = 0; f < npfx; f++)
+        if (pfx[(size_t)f + 1] - pfx[(size_t)f] == 2) dmap[(size_t)(f >> 6)] |= 1ull << (f & 63);
+    for (int w = 1; w < nwords; w++) dcnt[(size_t)w] = dcnt[(size_t)w - 1] + (uint32_t)__builtin_popcountll(dmap[(size_t)w - 1]);
+    const size_t lds_full = (size_t)M * 8 + (size_t)nwords * 12 + 64;
+    const bool lds_capture = lds_full <= 160 * 1024;
+    const size_t lds_bytes = lds_capture ? lds_full : (size_t)nwords * 12 + 64;
+    DBuf<uint64_t> dbl_map;
+    DBuf<uint32_t> dbl_cnt;
+    copy_up(dbl_map, dmap);
+    copy_up(dbl_cnt, dcnt);
+    if (lds_capture && lds_bytes > 64 * 1024)
+        HIPCHK(hipFuncSetAttribute((const void *)k_capture_g<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    // ---- chunks of records: as many as the per-record scratch (16 B per mask) and a bound on the bases allow; the staging
+    // buffers are sized from the bases of the largest chunk with the synthetic builder's estimate per record
+    const int64_t CH_MAX = std::max<int64_t>(1, std::min<int64_t>(2048, ((int64_t)128 << 20) / ((int64_t)M * 16)));
+    const int64_t CH_BASES = (int64_t)1 << 30;
+    struct Chunk {
+        int64_t l0;
+        int n;
+        double seeds, pos;
+    };
+    std::vector<Chunk> chunks;
+    for (int64_t l = 0; l < nlocal;) {
+        Chunk c{l, 0, 0, 0};
+        int64_t bases = 0;
+        while (l < nlocal && c.n < CH_MAX && (c.n == 0 || bases + glen[(size_t)l] <= CH_BASES)) {
+            bases += glen[(size_t)l];
+            c.seeds += 2.0 * (1.45 * M + (double)glen[(size_t)l] / 42.0) + 1024;
+            c.pos += 1.45 * M + 64;
+            c.n++;
+            l++;
+        }
+        chunks.push_back(c);
+    }
+    int ch_n = 1;
+    double est_seeds = 0, est_pos = 0;
+    for (auto &c : chunks) {
+        ch_n = std::max(ch_n, c.n);
+        est_seeds = std::max(est_seeds, c.seeds);
+        est_pos = std::max(est_pos, c.pos);
+    }
+    unsigned long long cap = (unsigned long long)est_seeds + 65536, pos_cap = (unsigned long long)est_pos + (unsigned long long)ch_n + 64;
+    if (b->stage_seeds > 0) { // (tests: a first estimate that is too small, so that the enlarge-and-retry path runs)
+        cap = (unsigned long long)b->stage_seeds;
+        pos_cap = (unsigned long long)b->stage_seeds + (unsigned long long)ch_n + 64;
+    }
+    DBuf<uint16_t> s_mask;
+    DBuf<uint64_t> s_kmer, s_val, pos_keys, pos_keys2;
+    auto size_staging = [&]() {
+        s_mask.alloc_exact(cap);
+        s_kmer.alloc_exact(cap);
+        s_val.alloc_exact(cap);
+        pos_keys.alloc_exact(pos_cap);
+        pos_keys2.alloc_exact(pos_cap);
+    };
+    size_staging();
+    DBuf<unsigned long long> counters, hashes;
+    counters.ensure(8);
+    hashes.alloc_exact(lds_capture ? 1 : (size_t)ch_n * M);
+    DBuf<uint32_t> miss_pos, miss_cnt;
+    miss_pos.alloc_exact((size_t)ch_n * M);
+    miss_cnt.alloc_exact((size_t)ch_n * M);
+    SeedPacker packer;
+    packer.begin(ix, nlocal, b->max_len);
+    double t_cap = 0, t_desert = 0, t_pack = 0;
+    // the seeds of one chunk in the staging arrays; false: an array was too small - `cap` / `pos_cap` are what it takes
+    // (nothing was written past an array: every store is guarded by its capacity)
+    auto generate = [&](const Chunk &c, unsigned long long &nseeds) {
+        const unsigned long long pos_lim = pos_cap - (unsigned long long)c.n - 1;
+        const double ta = now_ms();
+        HIPCHK(hipMemsetAsync(counters.p, 0, 2 * sizeof(unsigned long long), ix->st));
+        if (lds_capture)
+            hipLaunchKernelGGL(k_capture_g<true>, dim3(c.n), dim3(1024), lds_bytes, ix->st, gt, mt, ix->d_gbits.p, c.l0, dbl_map.p, dbl_cnt.p,
+                               hashes.p, miss_pos.p, miss_cnt.p, s_mask.p, s_kmer.p, s_val.p, counters.p, cap, pos_keys.p, counters.p + 1, pos_lim, dbg ? counters.p + 4 : nullptr);
+        else
+            hipLaunchKernelGGL(k_capture_g<false>, dim3(c.n), dim3(1024), lds_bytes, ix->st, gt, mt, ix->d_gbits.p, c.l0, dbl_map.p, dbl_cnt.p,
+                               hashes.p, miss_pos.p, miss_cnt.p, s_mask.p, s_kmer.p, s_val.p, counters.p, cap, pos_keys.p, counters.p + 1, pos_lim, dbg ? counters.p + 4 : nullptr);
+        HIPCHK(hipGetLastError());
+        unsigned long long hc[8];
+        HIPCHK(hipMemcpyAsync(hc, counters.p, sizeof hc, hipMemcpyDeviceToHost, ix->st));
+        bsync(ix);
+        const double tb = now_ms();
+        t_cap += tb - ta;
+        if (dbg)
+            fprintf(stderr, "[lm] genome builder: capture of record %lld (%d bases): argmin %.3f ms, missing-prefix pass %.3f ms, emit %.3f ms\n",
+                    (long long)c.l0, glen[(size_t)c.l0], (double)(hc[5] - hc[4]) * 1e-5, (double)(hc[6] - hc[5]) * 1e-5, (double)(hc[7] - hc[6]) * 1e-5);
+        if (hc[0] >= cap || hc[1] >= pos_lim) {
+            // (desert and reversed seeds come on top of the captures: about as many again, twice over)
+            cap = std::max(cap, hc[0] * 4 + 65536);
+            pos_cap = std::max(pos_cap, hc[1] * 2 + (unsigned long long)ch_n + 64);
+            return false;
+        }
+        unsigned long long npk = hc[1];
+        hipLaunchKernelGGL(k_pseudo_pos_g, dim3((c.n + 63) / 64), dim3(64), 0, ix->st, gt, c.l0, c.n, K, pos_keys.p, npk);
+        npk += (unsigned long long)c.n;
+        prim_sort_keys(ix->st, ix->tmp, pos_keys.p, pos_keys2.p, (size_t)npk, 0, 64);
+        hipLaunchKernelGGL(k_desert_fill_g, dim3(gridn(((int64_t)npk + 63) / 64, 4)), dim3(256), 0, ix->st, gt, mt, ix->d_gbits.p, c.l0,
+                           pos_keys2.p, (int64_t)npk, bo.max_desert, bo.seed_dist, s_mask.p, s_kmer.p, s_val.p, counters.p, cap);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(hc, counters.p, sizeof hc, hipMemcpyDeviceToHost, ix->st));
+        bsync(ix);
+        if (hc[0] >= cap) {
+            cap = hc[0] * 3 + 65536;
+            return false;
+        }
+        const unsigned long long upto = hc[0];
+        hipLaunchKernelGGL(k_reverse_seeds, dim3(gridn((int64_t)upto)), dim3(256), 0, ix->st, mt, 0ull, upto, s_mask.p, s_kmer.p, s_val.p,
+                           counters.p, cap);
+        HIPCHK(hipMemcpyAsync(hc, counters.p, sizeof hc, hipMemcpyDeviceToHost, ix->st));
+        bsync(ix);
+        if (hc[0] >= cap) {
+            cap = hc[0] + hc[0] / 4 + 65536;
+            return false;
+        }
+        nseeds = hc[0];
+        t_desert += now_ms() - tb;
+        return true;
+    };
+    for (int pass = 0; pass < 2; pass++) {
+        for (const Chunk &c : chunks) {
+            unsigned long long n = 0;
+            for (int attempt = 0; !generate(c, n); attempt++) {
+                // a record set that outgrows the estimate (a k-mer repeated thousands of times under many masks) takes a larger try
+                if (attempt >= 4) throw HipError("genome builder: the seed staging buffers outgrew four enlargements");
+                if (dbg) fprintf(stderr, "[lm] genome builder: staging buffers enlarged to %llu seeds / %llu positions\n", cap, pos_cap);
+                size_staging();
+            }
+            const double tc = now_ms();
+            if (pass == 0) packer.count(s_mask.p, s_kmer.p, s_val.p, (int64_t)n);
+            else packer.place(s_mask.p, s_kmer.p, s_val.p, (int64_t)n);
+            bsync(ix);
+            t_pack += now_ms() - tc;
+        }
+        if (pass == 0) packer.end_count();
+        if (dbg)
+            fprintf(stderr, "[lm] genome builder pass %d: capture %.1f ms, desert+reverse %.1f ms, packer %.1f ms (cumulative)\n", pass, t_cap,
+                    t_desert, t_pack);
+    }
+    hashes.release();
+    miss_pos.release();
+    miss_cnt.release();
+    pos_keys.release();
+    pos_keys2.release();
+    s_mask.release();
+    s_kmer.release();
+    s_val.release();
+    const double tf = now_ms();
+    packer.finish();
+    if (dbg)
+        fprintf(stderr, "[lm] genome builder: partition sort %.1f ms; %lld records, %lld seeds (%lld outliers); finish %.1f ms\n", now_ms() - tf,
+                (long long)nlocal, (long long)ix->n_seeds, (long long)ix->n_seeds_outlier, now_ms() - t0);
+    ix->tmp.release();
+    // ---- residency, as lm_index_build_synthetic_ex: built in HBM, then the records beyond the budget move to pinned host memory
+    ix->res.genomes_device = nlocal;
+    ix->res.genome_bytes_device = b->store_bytes;
+    {
+        int64_t budget = rq.budget;
+        if (rq.mode == LM_GENOMES_AUTO && budget == 0) {
+            size_t fr = 0, tot = 0;
+            HIPCHK(hipMemGetInfo(&fr, &tot));
+            budget = lm_res_auto_budget((int64_t)fr + b->store_bytes, 0);
+        }
+        int64_t keep = rq.mode == LM_GENOMES_HOST ? 0 : nlocal;
+        if (rq.mode == LM_GENOMES_AUTO)
+            for (keep = 0; keep < nlocal && goff[(size_t)keep] + slot[(size_t)keep] <= budget;) keep++;
+        if (keep < nlocal) {
+            const int64_t kept_bytes = keep > 0 ? goff[(size_t)keep - 1] + slot[(size_t)keep - 1] : 0;
+            std::vector<int64_t> nbs;
+            for (int64_t l = keep; l < nlocal; l++) nbs.push_back(((int64_t)glen[(size_t)l] + 3) >> 2);
+            ResidencyPlan plan = plan_residency(nbs, LM_GENOMES_HOST, 0, LM_RES_SEGMENT_BYTES);
+            plan.place.insert(plan.place.begin(), (size_t)keep, GenomePlace()); // (the kept records: in the device store)
+            plan.genomes_device = keep;
+            plan.bytes_device = kept_bytes;
+            std::string e;
+            if (!lm_res_alloc_host(ix, plan, e)) throw DeviceOOM(e); // (LM_ERR_NOMEM with the text)
+            for (int64_t l = keep; l < nlocal; l++) {
+                const GenomePlace &pl = plan.place[(size_t)l];
+                HIPCHK(hipMemcpyAsync(ix->g_host_segs[(size_t)pl.seg].p + pl.off, ix->d_gbits.p + goff[(size_t)l], (size_t)nbs[(size_t)(l - keep)],
+                                      hipMemcpyDeviceToHost, ix->st));
+                h.genomes[(size_t)l].bits_off = -1; // (not in the device store)
+                goff[(size_t)l] = -1;
+            }
+            bsync(ix);
+            {   // the device store shrinks to the records that stay (same offsets: they are its first bytes)
+                DBuf<uint8_t> kept;
+                kept.alloc_exact((size_t)kept_bytes + 64, true, ix->st);
+                if (kept_bytes > 0) HIPCHK(hipMemcpyAsync(kept.p, ix->d_gbits.p, (size_t)kept_bytes, hipMemcpyDeviceToDevice, ix->st));
+                bsync(ix);
+                ix->d_gbits.release();
+                std::swap(ix->d_gbits.p, kept.p);
+                std::swap(ix->d_gbits.cap, kept.cap);
+            }
+            copy_up(ix->d_g_off, goff);
+            bsync(ix);
+            ix->view.gbits = ix->d_gbits.p;
+        }
+    }
+    ix->hbm_bytes = ix->seed_bytes + (int64_t)((uint64_t)ix->res.genome_bytes_device + 64 + (uint64_t)M * 8 + pfx.size() * 4 + (uint64_t)nlocal * 20 +
+                                               h.batch_first.size() * 8);
+    lm_set_scratch_budget(ix);
+}
+
+} // namespace lm
+
+extern "C" {
+
+void lm_build_opt_default(lm_build_opt *o) {
+    if (!o) return;
+    o->k = 31;
+    o->masks = 20000;            // index.go:560
+    o->mask_seed = 1;
+    o->max_desert = 100;         // index.go:582
+    o->seed_dist = 50;           // index.go:584
+    o->contig_interval = 1000;   // index.go:619
+    o->genome_batch_size = 5000; // index.go:613
+    o->max_genome = 20000000;    // index.go:538
+}
+
+lm_status lm_index_builder_new(const lm_build_opt *bo, const lm_options *opt, const lm_residency *res, int device, lm_index_builder **out) {
+    if (!out) return LM_ERR_ARG;
+    *out = nullptr;
+    if (!bo || !opt) {
+        g_open_error = "lm_index_builder_new: build options and search options are needed";
+        return LM_ERR_ARG;
+    }
+    lm_res_request rq;
+    {
+        const lm_status rs = lm_res_resolve(res, rq, g_open_error);
+        if (rs != LM_OK) return rs;
+    }
+    if (bo->k != 31 || bo->masks < 4 || bo->masks > 65535 || bo->genome_batch_size < 1 || bo->genome_batch_size > (1 << 17) ||
+        bo->max_desert < 1 || bo->seed_dist < 1 || bo->contig_interval < 0 || bo->contig_interval >= (1 << 28) || bo->max_genome >= (1 << 28)) {
+        g_open_error = "lm_index_builder_new: unsupported build options (k must be 31, masks in [4, 65535], genome_batch_size in [1, 2^17], "
+                       "max_desert and seed_dist >= 1, contig_interval >= 0, max_genome < 2^28)";
+        return LM_ERR_ARG;
+    }
+    const int p = std::max(1, (int)(std::log2((double)bo->masks) / 2));
+    if (bo->masks > 2 * (1 << (2 * p))) { // (gen_masks: every p-base prefix once, the rest on distinct prefixes)
+        g_open_error = "lm_index_builder_new: " + std::to_string(bo->masks) + " masks need more than two masks per " + std::to_string(p) +
+                       "-base prefix, which the mask generator of this build does not make (at most " + std::to_string(2 * (1 << (2 * p))) + ")";
+        return LM_ERR_ARG;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
+        (void)hipGetLastError();
+        g_open_error = "no HIP device available (this library has no CPU path)";
+        return LM_ERR_NO_DEVICE;
+    }
+    std::unique_ptr<lm_index_builder> b(new lm_index_builder());
+    b->bo = *bo;
+    b->rq = rq;
+    // measurement / tests only; results do not depend on either
+    if (const char *e = getenv("LM_BUILD_SLAB_KB")) b->slab_bytes = std::max<int64_t>(64, atoll(e)) << 10; // many small slabs
+    if (const char *e = getenv("LM_BUILD_STAGE_SEEDS")) b->stage_seeds = std::max<int64_t>(1024, atoll(e)); // staging arrays that overflow
+    try {
+        lm_index *ix = new lm_index();
+        b->ix = ix;
+        ix->opt = *opt;
+        ix->device = device;
+        HIPCHK(hipSetDevice(device));
+        HIPCHK(hipStreamCreate(&ix->st));
+        HostIndex &h = ix->host;
+        const int K = bo->k, M = bo->masks;
+        h.k = K;
+        h.M = M;
+        h.main_version = 3;
+        h.minor_version = 5;
+        h.synthetic = false;
+        h.mask_prefix = p;
+        h.anchor_prefix = 6;
+        h.contig_interval = bo->contig_interval;
+        h.shard_rank = opt->shard_count > 1 ? opt->shard_rank : 0;
+        h.shard_count = opt->shard_count > 1 ? opt->shard_count : 1;
+        if (h.shard_rank < 0 || h.shard_rank >= h.shard_count) {
+            g_open_error = "lm_index_builder_new: shard_rank outside [0, shard_count)";
+            return LM_ERR_OPTION;
+        }
+        if (opt->min_prefix > K || opt->min_prefix < p + h.anchor_prefix) {
+            g_open_error = "MinPrefix out of range for this index";
+            return LM_ERR_OPTION;
+        }
+        gen_masks(K, M, (uint64_t)bo->mask_seed, h.masks);
+        b->pfx.assign((size_t)(1ull << (2 * p)) + 1, 0);
+        for (int i = 0; i < M; i++) b->pfx[(size_t)(h.masks[(size_t)i] >> ((K - p) << 1)) + 1]++;
+        for (size_t i = 1; i < b->pfx.size(); i++) {
+            if (b->pfx[i] < 1 || b->pfx[i] > 2) throw HipError("genome builder: the mask set does not have every prefix once or twice");
+            b->pfx[i] += b->pfx[i - 1];
+        }
+        ix->d_masks.ensure((size_t)M);
+        ix->d_pfx_first.ensure(b->pfx.size());
+        HIPCHK(hipMemcpyAsync(ix->d_masks.p, h.masks.data(), (size_t)M * 8, hipMemcpyHostToDevice, ix->st));
+        HIPCHK(hipMemcpyAsync(ix->d_pfx_first.p, b->pfx.data(), b->pfx.size() * 4, hipMemcpyHostToDevice, ix->st));
+        bsync(ix);
+    } catch (const std::exception &e) {
+        g_open_error = e.what();
+        return LM_ERR_HIP;
+    }
+    *out = b.release();
+    return LM_OK;
+}
+
+lm_status lm_index_builder_add(lm_index_builder *b, const char *genome_id, const lm_contig *contigs, size_t ncontigs) {
+    if (!b) return LM_ERR_ARG;
+    if (b->broken) {
+        b->err = "lm_index_builder_add: an earlier device error left this builder unusable: " + b->err;
+        return LM_ERR_HIP;
+    }
+    if (!genome_id || (!contigs && ncontigs > 0)) {
+        b->err = "lm_index_builder_add: genome id and contigs are needed";
+        return LM_ERR_ARG;
+    }
+    for (size_t i = 0; i < ncontigs; i++)
+        if (!contigs[i].id || (!contigs[i].seq && contigs[i].len > 0)) {
+            b->err = std::string("lm_index_builder_add: contig without id or sequence in genome ") + genome_id;
+            return LM_ERR_ARG;
+        }
+    lm_index *ix = b->ix;
+    HostIndex &h = ix->host;
+    const lm_build_opt &bo = b->bo;
+    std::vector<uint32_t> lens(ncontigs);
+    std::vector<const uint8_t *> seqs(ncontigs);
+    int64_t bases = 0;
+    for (size_t i = 0; i < ncontigs; i++) {
+        lens[i] = contigs[i].len;
+        seqs[i] = contigs[i].seq;
+        bases += contigs[i].len;
+    }
+    std::vector<BuildRecord> recs;
+    const int rc = plan_genome_records(lens.data(), ncontigs, bo.k, bo.contig_interval, bo.max_genome, recs);
+    if (rc != BUILD_OK) {
+        const int64_t maxg = bo.max_genome > 0 ? bo.max_genome : ((int64_t)1 << 28) - 1;
+        b->err = std::string("genome ") + genome_id + " not added: " +
+                 (rc == BUILD_NO_CONTIG    ? std::string("it has no contig")
+                  : rc == BUILD_BIG_CONTIG ? "skipping a big genome with a sequence longer than max_genome (" + std::to_string(maxg) + " bp)"
+                  : rc == BUILD_SHORT      ? "a genome record shorter than k = " + std::to_string(bo.k) + " bases"
+                                           : std::string("a genome record of 2^28 bases or more"));
+        return LM_ERR_ARG;
+    }
+    const bool keep = build_shard_keeps(b->nrecords, h.shard_count, h.shard_rank);
+    // the device work of every record first, then the tables: a failure leaves nothing of the genome behind
+    std::vector<int64_t> offs(recs.size(), 0);
+    std::vector<std::vector<BuildRegion>> regs(recs.size());
+    if (keep) {
+        const size_t nslabs0 = b->slabs.size();
+        const int64_t used0 = nslabs0 ? b->slabs.back()->used : 0, store0 = b->store_bytes;
+        try {
+            HIPCHK(hipSetDevice(ix->device));
+            for (size_t r = 0; r < recs.size(); r++) {
+                offs[r] = builder_pack(b, recs[r], contigs);
+                plan_skip_regions(recs[r], seqs.data(), lens.data(), bo.contig_interval, regs[r]);
+            }
+        } catch (const std::exception &e) {
+            b->err = e.what();
+            if (hipStreamSynchronize(ix->st) != hipSuccess) b->broken = true;
+            (void)hipGetLastError();
+            b->slabs.resize(nslabs0);
+            if (nslabs0) b->slabs.back()->used = used0;
+            b->store_bytes = store0;
+            return dynamic_cast<const DeviceOOM *>(&e) ? LM_ERR_NOMEM : LM_ERR_HIP;
+        }
+    }
+    for (size_t r = 0; r < recs.size(); r++) {
+        const BuildRecord &R = recs[r];
+        HostGenome G;
+        G.bg = build_genome_key(b->nrecords, bo.genome_batch_size);
+        G.global = b->nrecords;
+        G.id = genome_id;
+        G.genome_size = (int32_t)R.bases;
+        G.len = R.len;
+        G.nseqs = R.n;
+        for (int c = 0; c < R.n; c++) {
+            G.seq_sizes.push_back((int32_t)contigs[R.first + c].len);
+            G.seq_ids.emplace_back(contigs[R.first + c].id);
+        }
+        if (recs.size() > 1) h.chunk_of[G.bg] = HostIndex::ChunkInfo{b->nlists, (int)recs.size(), (int)r};
+        if (h.shard_count > 1) b->g2local.push_back(keep ? (int32_t)h.genomes.size() : -1);
+        if (keep) {
+            G.bits_off = offs[r];
+            for (const BuildRegion &g : regs[r]) {
+                b->reg_s.push_back(g.s);
+                b->reg_e.push_back(g.e);
+            }
+            b->reg_off.push_back((int32_t)b->reg_s.size());
+            b->max_len = std::max<int64_t>(b->max_len, R.len);
+            h.genomes.push_back(std::move(G));
+        } else {
+            G.bits_off = -1;
+            h.other_of[G.bg] = (int)h.others.size();
+            h.others.push_back(std::move(G));
+        }
+        b->nrecords++;
+    }
+    if (recs.size() > 1) b->nlists++;
+    b->ninput++;
+    b->input_bases += bases;
+    return LM_OK;
+}
+
+lm_status lm_index_builder_finish(lm_index_builder *bp, lm_index **out) {
+    if (out) *out = nullptr;
+    std::unique_ptr<lm_index_builder> b(bp); // consumed whatever happens
+    if (!bp || !out) return LM_ERR_ARG;
+    if (b->broken) {
+        g_open_error = "lm_index_builder_finish: an earlier device error left this builder unusable: " + b->err;
+        return LM_ERR_HIP;
+    }
+    if (b->nrecords == 0 || b->ix->host.genomes.empty()) {
+        g_open_error = b->nrecords == 0 ? "lm_index_builder_finish: no genome was added" : "lm_index_builder_finish: no genome of this shard was added";
+        return LM_ERR_ARG;
+    }
+    try {
+        HIPCHK(hipSetDevice(b->ix->device));
+        builder_finish(b.get(), b->rq);
+    } catch (const DeviceOOM &e) {
+        g_open_error = e.what();
+        return LM_ERR_NOMEM;
+    } catch (const std::exception &e) {
+        g_open_error = e.what();
+        return LM_ERR_HIP;
+    }
+    *out = b->ix;
+    b->ix = nullptr;
+    return LM_OK;
+}
+
+void lm_index_builder_free(lm_index_builder *b) { delete b; }
+
+const char *lm_index_builder_last_error(const lm_index_builder *b) { return b ? b->err.c_str() : g_open_error.c_str(); }
 
 } // extern "C"

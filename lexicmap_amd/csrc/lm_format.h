@@ -28,6 +28,10 @@ struct HostIndex {
     int64_t total_bases = 0;
     int contig_interval = 1000;
     int genome_batches = 0;
+    int genome_batch_size = 5000;  // records per genome batch of a set built here (lm_index_save; the loader counts the batch files)
+    int64_t rand_seed = 1;         // build settings lm_index_save writes into info.toml (a search reads none of them): the defaults
+    int max_seed_dist = 100, seed_dist_in_desert = 50; // of `lexicmap index` unless lm_index_builder knew better
+    int64_t input_genomes = 0;     // input genomes of a set built by lm_index_builder (a split genome has several records); 0: one per record
     std::vector<uint64_t> masks;
     std::vector<std::string> seed_files; // seeds/chunk_NNN.bin, sorted
     // genomes of this shard

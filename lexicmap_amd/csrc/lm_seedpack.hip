@@ -640,7 +640,8 @@ extern "C" lm_status lm_index_save(lm_index *ix, const char *dir_c, int chunks) 
         // info.toml names the number of chunk FILES: ceil(M / ceil(M / chunks)) of them are written (M = 100 masks asked into 16
         // chunks are 15 files of 7 masks), as the reference's writer and the oracle's do
         chunks = (M + (M + chunks - 1) / chunks - 1) / ((M + chunks - 1) / chunks);
-        const int nbatches = std::max(1, h.genome_batches > 0 ? h.genome_batches : (int)((h.genomes.size() + 4999) / 5000));
+        const int bsz = h.genome_batch_size > 0 ? h.genome_batch_size : 5000;
+        const int nbatches = std::max(1, h.genome_batches > 0 ? h.genome_batches : (int)((h.genomes.size() + (size_t)bsz - 1) / (size_t)bsz));
         const bool use7 = nbatches <= 512; // kv-data.go:137
         if (!make_dir(dir) || !make_dir(dir + "/seeds") || !make_dir(dir + "/genomes")) throw HipError("lm_index_save: cannot create " + dir);
         // ---- masks.bin (this build's layout, lm_format.cpp) and info.toml
@@ -660,17 +661,18 @@ extern "C" lm_status lm_index_save(lm_index *ix, const char *dir_c, int chunks) 
             OutFile f(dir + "/info.toml");
             char t[1024];
             const int n = snprintf(t, sizeof t,
-                                   "# Index format\nmain-version = 3\nminor-version = 5\n# LexicHash\nmax-K = %d\nmasks = %d\nrand-seed = 1\n"
-                                   "# Seed distance\nmax-seed-dist = 100\nseed-dist-in-desert = 50\n# Seeds (k-mer-value data) files\nchunks = %d\n"
+                                   "# Index format\nmain-version = 3\nminor-version = 5\n# LexicHash\nmax-K = %d\nmasks = %d\nrand-seed = %lld\n"
+                                   "# Seed distance\nmax-seed-dist = %d\nseed-dist-in-desert = %d\n# Seeds (k-mer-value data) files\nchunks = %d\n"
                                    "index-partitions = %d\n# Input genomes\ninput-genomes = %lld\ninput-bases = %lld\n# Genome data\ngenomes = %lld\n"
-                                   "genome-batch-size = 5000\ngenome-batches = %d\ncontig-interval = %d\n",
-                                   K, M, chunks, 1 << (2 * h.anchor_prefix), (long long)h.genomes.size(),
-                                   (long long)(h.total_bases > 0 ? h.total_bases : gbases), (long long)h.genomes.size(), nbatches,
+                                   "genome-batch-size = %d\ngenome-batches = %d\ncontig-interval = %d\n",
+                                   K, M, (long long)h.rand_seed, h.max_seed_dist, h.seed_dist_in_desert, chunks, 1 << (2 * h.anchor_prefix), (long long)(h.input_genomes > 0 ? h.input_genomes : (int64_t)h.genomes.size()),
+                                   (long long)(h.total_bases > 0 ? h.total_bases : gbases), (long long)h.genomes.size(), bsz, nbatches,
                                    h.contig_interval);
             f.put(t, (size_t)n);
             if (f.bad) throw HipError("lm_index_save: write failed (info.toml)");
         }
-        // ---- genomes: batches of 5000 in dense order, bases straight from the 2-bit store in HBM
+        // ---- genomes: the batches (5000 records each unless the set was built with another batch size) in dense order, bases
+        // straight from the 2-bit store in HBM
         {
             OutFile fmap(dir + "/genomes.map.bin");
             std::vector<uint8_t> bits;
