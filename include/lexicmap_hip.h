@@ -141,7 +141,7 @@ lm_status lm_index_get_residency(const lm_index *idx, lm_residency_info *info);
  *     seeds, packed seed image; `res` of _new is honoured as by lm_index_build_synthetic_ex.  The builder is consumed whether
  *     finish succeeds or not; after a failure lm_last_error(NULL) has the text.  LM_ERR_ARG when nothing was added.
  * Not done here (nor by the reference at this point): reading FASTA / gz files, soft-masking, --max-kmer-freq, merging
- * several builds; k must be 31 and the mask set may have at most two masks per p-base prefix (masks <= 2 * 4^p). */
+ * two finished indexes (genomes are ADDED to a resident one by lm_index_builder_extend); k must be 31 and the mask set may have at most two masks per p-base prefix (masks <= 2 * 4^p). */
 typedef struct lm_build_opt {      /* lm_build_opt_default(): the defaults of `lexicmap index` (index.go:538-619) */
     int32_t k;                     /* 31 (only 31 is accepted, as in lm_index_build_synthetic) */
     int32_t masks;                 /* 20000; [4, 65535] with at most two masks per p-base prefix, p = max(1, floor(log4 masks)):
@@ -164,6 +164,23 @@ lm_status lm_index_builder_add(lm_index_builder *b, const char *genome_id, const
 lm_status lm_index_builder_finish(lm_index_builder *b, lm_index **out); /* consumes b on success and on failure */
 void lm_index_builder_free(lm_index_builder *b);                        /* abandon */
 const char *lm_index_builder_last_error(const lm_index_builder *b);
+/* A builder that continues `base`.  finish() gives a NEW handle holding base's genomes followed by the added ones: what one
+ * lm_index_builder_* build of all of them, in that order, with base's masks would have given (the same lists, keys, store
+ * and saved files).  Only the added records are captured; base's seeds are decoded from its image and packed again.
+ *   The device, the lm_options (shard_rank / shard_count and total_bases_override among them) and the masks are base's.
+ *   bo == NULL: k, masks, contig_interval, genome_batch_size, max_desert and seed_dist are what the handle carries (an opened
+ *     index: what its info.toml says), max_genome its default.  A non-NULL bo must agree with base in k, masks,
+ *     contig_interval and genome_batch_size (LM_ERR_ARG, the text names the field); its mask_seed is IGNORED, because the
+ *     masks are base's; its max_desert, seed_dist and max_genome apply to the added genomes.
+ *   Record numbers continue from base's record count over all shards; a shard keeps the genomes whose first record number
+ *     % shard_count == shard_rank.  Every batch of base but the last must hold exactly genome_batch_size records: a base
+ *     with irregular batches (an index of the reference with split genomes is one) is refused with LM_ERR_ARG.
+ *   add / finish / free / last_error work as on a builder of _new; finish with nothing added is LM_ERR_ARG.  base is only
+ *     read: it stays open, unchanged and searchable, the caller closes it - but it must stay open until finish or free has
+ *     returned, and finish holds base's lock while it reads.  The new handle starts without a genome filter.
+ *   base's image, the new image and the seed staging arrays are on the device together; LM_ERR_NOMEM (base intact, the
+ *     builder consumed) when they do not fit. */
+lm_status lm_index_builder_extend(lm_index *base, const lm_build_opt *bo, const lm_residency *res, lm_index_builder **out);
 /* bases [start, start+len) of local genome `local_genome` as ASCII (used to derive synthetic queries) */
 lm_status lm_index_fetch(lm_index *idx, int64_t local_genome, int64_t start, int64_t len, uint8_t *out);
 /* Writes the resident (unsharded) index to `dir`: info.toml, seeds/chunk_NNN.bin (+ .idx, kv/kv-data.go:126-602) in at most

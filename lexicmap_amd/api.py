@@ -157,6 +157,7 @@ def lib():
     L.lm_build_opt_default.argtypes = [C.POINTER(BuildOpt)]
     L.lm_build_opt_default.restype = None
     L.lm_index_builder_new.argtypes = [C.POINTER(BuildOpt), C.POINTER(Options), C.POINTER(Residency), C.c_int, C.POINTER(vp)]
+    L.lm_index_builder_extend.argtypes = [vp, C.POINTER(BuildOpt), C.POINTER(Residency), C.POINTER(vp)]
     L.lm_index_builder_add.argtypes = [vp, C.c_char_p, C.POINTER(Contig), C.c_size_t]
     L.lm_index_builder_finish.argtypes = [vp, C.POINTER(vp)]
     L.lm_index_builder_free.argtypes = [vp]
@@ -302,6 +303,18 @@ class Index:
         in __init__.  A genome the builder refuses (LM_ERR_ARG: a contig longer than max_genome, a record shorter than k)
         raises ValueError with the builder's text; nothing of it is added."""
         b = IndexBuilder(build_opt, options, device, residency)
+        try:
+            for gid, contigs in genomes:
+                b.add(gid, contigs)
+            return b.finish()
+        finally:
+            b.close()
+
+    def extend(self, genomes, build_opt=None, residency=None):
+        """a NEW Index holding this one's genomes followed by `genomes` (lm_index_builder_extend): what one from_genomes build
+        of all of them with this index's masks gives, without capturing this index's genomes again.  self stays open and
+        unchanged.  build_opt None: the settings this index was built with; genomes and residency as in from_genomes."""
+        b = IndexBuilder.extending(self, build_opt, residency)
         try:
             for gid, contigs in genomes:
                 b.add(gid, contigs)
@@ -622,6 +635,25 @@ class IndexBuilder:
             e.status = st
             raise e
         self.h = h
+
+    @classmethod
+    def extending(cls, index, build_opt=None, residency=None):
+        """lm_index_builder_extend: a builder that continues `index`, which must stay open until finish() or close()"""
+        L = lib()
+        self = cls.__new__(cls)
+        self.opt = index.opt
+        self.bo = build_opt
+        self.device = 0
+        self.base = index  # (kept alive for as long as the builder reads it)
+        h = C.c_void_p()
+        st = L.lm_index_builder_extend(index.h, C.byref(build_opt) if build_opt is not None else None,
+                                       C.byref(residency) if residency is not None else None, C.byref(h))
+        if st != 0:
+            e = RuntimeError("lm_index_builder_extend failed (%d): %s" % (st, L.lm_last_error(None).decode()))
+            e.status = st
+            raise e
+        self.h = h
+        return self
 
     def last_error(self):
         return lib().lm_index_builder_last_error(self.h).decode()

@@ -1261,6 +1261,11 @@ struct lm_index_builder {
     std::vector<std::unique_ptr<Slab>> slabs;
     int64_t slab_bytes = (int64_t)256 << 20, store_bytes = 0;
     int64_t stage_seeds = 0;          // > 0 (LM_BUILD_STAGE_SEEDS): first size of the seed staging arrays instead of the estimate
+    // lm_index_builder_extend: the index this builder continues (borrowed, only read), how many of ix->host.genomes are its
+    // local records (they lie in front, their store slots planned but not filled before finish) and its record count over all shards
+    lm_index *base = nullptr;
+    int64_t nbase = 0, base_records = 0;
+    int64_t piece_seeds = 0;          // > 0 (LM_BUILD_STAGE_SEEDS): the base's seeds are decoded in pieces of at most this many
     std::vector<int32_t> reg_off{0}, reg_s, reg_e; // skip regions of the local records (CSR)
     std::vector<int32_t> g2local;                  // sharded: record number -> local number or -1
     std::vector<int32_t> pfx;
@@ -1343,13 +1348,47 @@ static void builder_finish(lm_index_builder *b, const lm_res_request &rq) {
         if (s->used > 0) HIPCHK(hipMemcpyAsync(ix->d_gbits.p + s->first, s->d.p, (size_t)s->used, hipMemcpyDeviceToDevice, ix->st));
     bsync(ix);
     b->slabs.clear();
+    const lm_index *base = b->base;
+    const int64_t nbase = b->nbase;
+    if (base) {
+        // the base's records into the slots planned for them in front of the added ones, record by record: an opened index
+        // packs its store more tightly than build_slot_bytes, and a host-resident record comes from its pinned segment.
+        // Device records whose slots lie as far apart here as there (a base built by this builder) go as one copy.
+        int64_t run_src = -1, run_dst = 0, run_len = 0;
+        auto flush = [&]() {
+            if (run_src >= 0) HIPCHK(hipMemcpyAsync(ix->d_gbits.p + run_dst, base->d_gbits.p + run_src, (size_t)run_len, hipMemcpyDeviceToDevice, ix->st));
+            run_src = -1;
+        };
+        for (int64_t l = 0; l < nbase; l++) {
+            const HostGenome &G = h.genomes[(size_t)l];
+            const int64_t nb = ((int64_t)G.len + 3) >> 2, src = base->host.genomes[(size_t)l].bits_off;
+            const uint8_t *hp = base->g_hhost.empty() ? nullptr : base->g_hhost[(size_t)l];
+            if (hp) {
+                flush();
+                HIPCHK(hipMemcpyAsync(ix->d_gbits.p + G.bits_off, hp, (size_t)nb, hipMemcpyHostToDevice, ix->st));
+                continue;
+            }
+            if (run_src >= 0 && src - run_src == G.bits_off - run_dst && src >= run_src + run_len) {
+                run_len = src - run_src + nb;
+                continue;
+            }
+            flush();
+            run_src = src;
+            run_dst = G.bits_off;
+            run_len = nb;
+        }
+        flush();
+        bsync(ix);
+    }
     // ---- tables
     h.total_bases = ix->opt.total_bases_override > 0 ? ix->opt.total_bases_override : b->input_bases;
     h.input_genomes = b->ninput;
     h.genome_batch_size = bo.genome_batch_size;
-    h.rand_seed = bo.mask_seed;
-    h.max_seed_dist = bo.max_desert;
-    h.seed_dist_in_desert = bo.seed_dist;
+    if (!base) { // (a continued set keeps the settings it was begun with: _extend copied them from the base)
+        h.rand_seed = bo.mask_seed;
+        h.max_seed_dist = bo.max_desert;
+        h.seed_dist_in_desert = bo.seed_dist;
+    }
     h.genome_batches = (int)((b->nrecords + bo.genome_batch_size - 1) / bo.genome_batch_size);
     h.batch_first.assign((size_t)h.genome_batches + 1, 0);
     for (int i = 0; i <= h.genome_batches; i++) h.batch_first[(size_t)i] = std::min<int64_t>((int64_t)i * bo.genome_batch_size, b->nrecords);
@@ -1423,8 +1462,8 @@ static void builder_finish(lm_index_builder *b, const lm_res_request &rq) {
         int n;
         double seeds, pos;
     };
-    std::vector<Chunk> chunks;
-    for (int64_t l = 0; l < nlocal;) {
+    std::vector<Chunk> chunks; // (of the added records only: the base's seeds are decoded from its image, not captured again)
+    for (int64_t l = nbase; l < nlocal;) {
         Chunk c{l, 0, 0, 0};
         int64_t bases = 0;
         while (l < nlocal && c.n < CH_MAX && (c.n == 0 || bases + glen[(size_t)l] <= CH_BASES)) {
@@ -1444,6 +1483,19 @@ static void builder_finish(lm_index_builder *b, const lm_res_request &rq) {
         est_pos = std::max(est_pos, c.pos);
     }
     unsigned long long cap = (unsigned long long)est_seeds + 65536, pos_cap = (unsigned long long)est_pos + (unsigned long long)ch_n + 64;
+    // the base's seeds pass through the same arrays in pieces: large enough that a big image is not cut into thousands of launches
+    std::vector<int64_t> base_md_off, base_out_off;
+    int64_t base_main = 0, base_out = 0;
+    if (base) {
+        base_md_off.resize((size_t)2 * M + 1);
+        base_out_off.resize((size_t)2 * M + 1);
+        HIPCHK(hipMemcpyAsync(base_md_off.data(), base->d_md_off.p, base_md_off.size() * 8, hipMemcpyDeviceToHost, ix->st));
+        HIPCHK(hipMemcpyAsync(base_out_off.data(), base->d_out_off.p, base_out_off.size() * 8, hipMemcpyDeviceToHost, ix->st));
+        bsync(ix);
+        base_main = base_md_off.back();
+        base_out = base_out_off.back();
+        cap = std::max<unsigned long long>(cap, (unsigned long long)std::min<int64_t>(std::max(base_main, base_out), (int64_t)1 << 26));
+    }
     if (b->stage_seeds > 0) { // (tests: a first estimate that is too small, so that the enlarge-and-retry path runs)
         cap = (unsigned long long)b->stage_seeds;
         pos_cap = (unsigned long long)b->stage_seeds + (unsigned long long)ch_n + 64;
@@ -1520,7 +1572,34 @@ static void builder_finish(lm_index_builder *b, const lm_res_request &rq) {
         t_desert += now_ms() - tb;
         return true;
     };
+    double t_base = 0, t_dump = 0;
     for (int pass = 0; pass < 2; pass++) {
+        if (base) {
+            // the base's seeds first, decoded in pieces no larger than the staging arrays (a list longer than a piece is cut);
+            // every value is re-encoded by the packer: gid_bits / pos_bits of the extended set may be wider than the base's
+            const double tb0 = now_ms();
+            const int64_t piece = b->piece_seeds > 0 ? std::min<int64_t>(b->piece_seeds, (int64_t)cap) : (int64_t)cap;
+            for (int flat = 0; flat < 2; flat++) {
+                const int64_t total = flat ? base_out : base_main;
+                for (int64_t s0 = 0; s0 < total; s0 += piece) {
+                    const int64_t n = std::min<int64_t>(piece, total - s0);
+                    const double td0 = dbg ? (bsync(ix), now_ms()) : 0;
+                    sp_dump_range(base, ix->st, flat ? base_out_off : base_md_off, flat != 0, s0, s0 + n, s_mask.p, s_kmer.p, s_val.p);
+                    if (dbg) {
+                        bsync(ix);
+                        t_dump += now_ms() - td0;
+                    }
+                    if (pass == 0) packer.count(s_mask.p, s_kmer.p, s_val.p, n);
+                    else packer.place(s_mask.p, s_kmer.p, s_val.p, n);
+                }
+            }
+            bsync(ix);
+            t_base += now_ms() - tb0;
+            if (dbg)
+                fprintf(stderr, "[lm] genome builder pass %d: the base's %lld seeds (%lld outliers) decoded and packed in pieces of %lld: %.1f ms, "
+                                "of which the decode kernel %.1f ms (cumulative)\n", pass, (long long)(base_main + base_out), (long long)base_out,
+                        (long long)piece, t_base, t_dump);
+        }
         for (const Chunk &c : chunks) {
             unsigned long long n = 0;
             for (int attempt = 0; !generate(c, n); attempt++) {
@@ -1703,6 +1782,148 @@ lm_status lm_index_builder_new(const lm_build_opt *bo, const lm_options *opt, co
     return LM_OK;
 }
 
+// A builder that continues a resident index ("Adding genomes to a resident index").  Everything per record -
+// key, captures, desert seeds, reversed seeds - is a function of the record and its number alone, and the packer takes seeds
+// in any order: so the base's seeds are decoded from its image (k_sp_dump_range), the added records are captured, and finish()
+// packs both into the image one build of all the genomes would have given.  Here: the settings, the check that the base's
+// batches can be continued, and the base's host tables copied in front of what add() appends.
+lm_status lm_index_builder_extend(lm_index *base, const lm_build_opt *bo_in, const lm_residency *res, lm_index_builder **out) {
+    if (!out) return LM_ERR_ARG;
+    *out = nullptr;
+    if (!base) {
+        g_open_error = "lm_index_builder_extend: an index to continue is needed";
+        return LM_ERR_ARG;
+    }
+    lm_res_request rq;
+    {
+        const lm_status rs = lm_res_resolve(res, rq, g_open_error);
+        if (rs != LM_OK) return rs;
+    }
+    std::lock_guard<std::mutex> base_lock(base->mu);
+    const HostIndex &bh = base->host;
+    lm_build_opt bo;
+    lm_build_opt_default(&bo);
+    if (bo_in) {
+        const char *field = bo_in->k != bh.k                                   ? "k"
+                            : bo_in->masks != bh.M                             ? "masks"
+                            : bo_in->contig_interval != bh.contig_interval     ? "contig_interval"
+                            : bo_in->genome_batch_size != bh.genome_batch_size ? "genome_batch_size"
+                                                                               : nullptr;
+        if (field) {
+            g_open_error = std::string("lm_index_builder_extend: ") + field + " of the build options differs from the index that is continued";
+            return LM_ERR_ARG;
+        }
+        bo = *bo_in;
+    } else {
+        bo.max_desert = bh.max_seed_dist;
+        bo.seed_dist = bh.seed_dist_in_desert;
+    }
+    bo.k = bh.k;
+    bo.masks = bh.M;
+    bo.mask_seed = bh.rand_seed; // (the masks are the base's, whatever seed made them)
+    bo.contig_interval = bh.contig_interval;
+    bo.genome_batch_size = bh.genome_batch_size;
+    if (bo.k != 31 || bo.masks < 4 || bo.masks > 65535 || bo.genome_batch_size < 1 || bo.genome_batch_size > (1 << 17) || bo.max_desert < 1 ||
+        bo.seed_dist < 1 || bo.contig_interval < 0 || bo.contig_interval >= (1 << 28) || bo.max_genome >= (1 << 28)) {
+        g_open_error = "lm_index_builder_extend: unsupported settings (k must be 31, masks in [4, 65535], genome_batch_size in [1, 2^17], "
+                       "max_desert and seed_dist >= 1, contig_interval >= 0, max_genome < 2^28)";
+        return LM_ERR_ARG;
+    }
+    if (bh.synthetic && bh.shard_count > 1) {
+        g_open_error = "lm_index_builder_extend: a shard of a synthetic set cannot be continued (its records are numbered without a table)";
+        return LM_ERR_ARG;
+    }
+    // record n lies in batch n / genome_batch_size: every batch of the base but the last must be full
+    const int nb = bh.genome_batches;
+    bool regular = nb >= 1 && (int)bh.batch_first.size() == nb + 1 && bh.batch_first[0] == 0;
+    for (int i = 0; regular && i < nb; i++) {
+        const int64_t n = bh.batch_first[(size_t)i + 1] - bh.batch_first[(size_t)i];
+        regular = i + 1 < nb ? n == bo.genome_batch_size : (n >= 1 && n <= bo.genome_batch_size);
+    }
+    if (!regular) {
+        g_open_error = "lm_index_builder_extend: the genome batches of the index are irregular (not every batch but the last holds genome_batch_size = " +
+                       std::to_string(bo.genome_batch_size) + " records, as in an index of the reference with split genomes): its records cannot be numbered on";
+        return LM_ERR_ARG;
+    }
+    const int64_t base_records = bh.batch_first[(size_t)nb];
+    const int64_t nbase = (int64_t)bh.genomes.size();
+    if (bh.shard_count > 1 ? (int64_t)bh.g2local.size() != base_records : nbase != base_records) {
+        g_open_error = "lm_index_builder_extend: the record tables of the index do not agree with its batches";
+        return LM_ERR_ARG;
+    }
+    const int K = bh.k, M = bh.M, p = bh.mask_prefix;
+    std::unique_ptr<lm_index_builder> b(new lm_index_builder());
+    b->bo = bo;
+    b->rq = rq;
+    b->base = base;
+    b->nbase = nbase;
+    b->base_records = base_records;
+    b->nrecords = base_records;
+    b->ninput = bh.input_genomes > 0 ? bh.input_genomes : base_records;
+    b->input_bases = bh.total_bases;
+    if (const char *e = getenv("LM_BUILD_SLAB_KB")) b->slab_bytes = std::max<int64_t>(64, atoll(e)) << 10;
+    if (const char *e = getenv("LM_BUILD_STAGE_SEEDS")) {
+        b->piece_seeds = std::max<int64_t>(4, atoll(e)); // (the decode pieces may be smaller than what a capture needs)
+        b->stage_seeds = std::max<int64_t>(1024, atoll(e));
+    }
+    b->pfx.assign((size_t)(1ull << (2 * p)) + 1, 0);
+    for (int i = 0; i < M; i++) b->pfx[(size_t)(bh.masks[(size_t)i] >> ((K - p) << 1)) + 1]++;
+    for (size_t i = 1; i < b->pfx.size(); i++) {
+        if (b->pfx[i] < 1 || b->pfx[i] > 2) {
+            g_open_error = "lm_index_builder_extend: the mask set of the index does not have every " + std::to_string(p) + "-base prefix once or twice";
+            return LM_ERR_ARG;
+        }
+        b->pfx[i] += b->pfx[i - 1];
+    }
+    try {
+        lm_index *ix = new lm_index();
+        b->ix = ix;
+        ix->opt = base->opt;
+        ix->device = base->device;
+        HIPCHK(hipSetDevice(ix->device));
+        HIPCHK(hipStreamCreate(&ix->st));
+        HostIndex &h = ix->host;
+        h.k = K;
+        h.M = M;
+        h.main_version = 3;
+        h.minor_version = 5;
+        h.synthetic = false;
+        h.mask_prefix = p;
+        h.anchor_prefix = bh.anchor_prefix;
+        h.contig_interval = bh.contig_interval;
+        h.shard_rank = bh.shard_rank;
+        h.shard_count = bh.shard_count;
+        h.rand_seed = bh.rand_seed;
+        h.max_seed_dist = bh.max_seed_dist;
+        h.seed_dist_in_desert = bh.seed_dist_in_desert;
+        h.masks = bh.masks;
+        // the base's tables in front: add() appends to them as it does in a fresh builder
+        h.genomes = bh.genomes;
+        h.others = bh.others;
+        h.other_of = bh.other_of;
+        h.chunk_of = bh.chunk_of;
+        for (const auto &kv : bh.chunk_of) b->nlists = std::max(b->nlists, kv.second.list + 1);
+        if (h.shard_count > 1) b->g2local = bh.g2local;
+        b->reg_off.assign((size_t)nbase + 1, 0); // (no skip regions are needed for records that are not captured again)
+        for (int64_t l = 0; l < nbase; l++) {
+            HostGenome &G = h.genomes[(size_t)l];
+            G.bits_off = b->store_bytes; // its slot in the new store, filled by finish()
+            b->store_bytes += build_slot_bytes(G.len);
+            b->max_len = std::max<int64_t>(b->max_len, G.len);
+        }
+        ix->d_masks.ensure((size_t)M);
+        ix->d_pfx_first.ensure(b->pfx.size());
+        HIPCHK(hipMemcpyAsync(ix->d_masks.p, h.masks.data(), (size_t)M * 8, hipMemcpyHostToDevice, ix->st));
+        HIPCHK(hipMemcpyAsync(ix->d_pfx_first.p, b->pfx.data(), b->pfx.size() * 4, hipMemcpyHostToDevice, ix->st));
+        bsync(ix);
+    } catch (const std::exception &e) {
+        g_open_error = e.what();
+        return LM_ERR_HIP;
+    }
+    *out = b.release();
+    return LM_OK;
+}
+
 lm_status lm_index_builder_add(lm_index_builder *b, const char *genome_id, const lm_contig *contigs, size_t ncontigs) {
     if (!b) return LM_ERR_ARG;
     if (b->broken) {
@@ -1808,15 +2029,21 @@ lm_status lm_index_builder_finish(lm_index_builder *bp, lm_index **out) {
         g_open_error = "lm_index_builder_finish: an earlier device error left this builder unusable: " + b->err;
         return LM_ERR_HIP;
     }
-    if (b->nrecords == 0 || b->ix->host.genomes.empty()) {
-        g_open_error = b->nrecords == 0 ? "lm_index_builder_finish: no genome was added" : "lm_index_builder_finish: no genome of this shard was added";
+    if (b->nrecords == b->base_records || b->ix->host.genomes.empty()) {
+        g_open_error = b->nrecords == b->base_records ? "lm_index_builder_finish: no genome was added" : "lm_index_builder_finish: no genome of this shard was added";
         return LM_ERR_ARG;
     }
+    // (an extending builder reads the base's image and store: no search or save of the base runs meanwhile)
+    std::unique_lock<std::mutex> base_lock;
+    if (b->base) base_lock = std::unique_lock<std::mutex>(b->base->mu);
     try {
         HIPCHK(hipSetDevice(b->ix->device));
         builder_finish(b.get(), b->rq);
     } catch (const DeviceOOM &e) {
         g_open_error = e.what();
+        if (b->base)
+            g_open_error = "lm_index_builder_finish: the base's image, the extended image and the seed staging do not fit the device together (the base is "
+                           "intact): " + g_open_error;
         return LM_ERR_NOMEM;
     } catch (const std::exception &e) {
         g_open_error = e.what();

@@ -276,6 +276,13 @@ std::string load_index(const std::string &dir, int shard_rank, int shard_count, 
     out.contig_interval = (int)toml_int(text, "contig-interval", 1000);
     out.genome_batches = (int)toml_int(text, "genome-batches", 1);
     int partitions = (int)toml_int(text, "index-partitions", 4096);
+    // the build settings no search reads: lm_index_save writes them back, and lm_index_builder_extend continues the set with
+    // them (absent keys leave the defaults of `lexicmap index`)
+    out.max_seed_dist = (int)toml_int(text, "max-seed-dist", out.max_seed_dist);
+    out.seed_dist_in_desert = (int)toml_int(text, "seed-dist-in-desert", out.seed_dist_in_desert);
+    out.genome_batch_size = (int)toml_int(text, "genome-batch-size", out.genome_batch_size);
+    out.input_genomes = toml_int(text, "input-genomes", out.input_genomes);
+    out.rand_seed = toml_int(text, "rand-seed", out.rand_seed);
 
     // masks.bin.  Two layouts are accepted:
     //  (a) this build's own (magic LMMASKS1: k u8 at 8, count u32 at 12, masks from 24), written by the oracle's index writer;

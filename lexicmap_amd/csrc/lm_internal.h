@@ -421,6 +421,11 @@ struct SeedPacker {
     void place(const uint16_t *mask, const uint64_t *kmer, const uint64_t *val, int64_t n);
     void finish(); // sorts the partitions, fills ix->view / ix->n_seeds / ix->seed_bytes
 };
+// The seeds [s0, s1) of a resident image decoded on stream `st` into the arrays count() / place() take (k_sp_dump_range):
+// main seeds as md_off numbers them, or (flat) outliers as out_off does; `off` is the host's copy of that table, [2M + 1].
+// The caller keeps `src` from changing (its mutex) and the arrays at least s1 - s0 long.
+void sp_dump_range(const lm_index *src, hipStream_t st, const std::vector<int64_t> &off, bool flat, int64_t s0, int64_t s1,
+                   uint16_t *s_mask, uint64_t *s_kmer, uint64_t *s_val);
 } // namespace lm
 
 // Experiment / A-B switches of the kernels, read from the environment ONCE when the handle is created (a search never calls

@@ -14,6 +14,7 @@
 // finish() -> every partition sorted by key in place (one wavefront per partition, LDS bitonic network; partitions
 // shared words are merged with masked atomics).  No copy of the unpacked seeds ever exists.
 #include "lm_prims.h"
+#include "lm_seed_walk.h"
 
 #include <errno.h>
 #include <sys/stat.h>
@@ -286,6 +287,63 @@ __global__ void k_sp_dump_list(DevIndexView ix, uint32_t md, int64_t n_main, uin
         kmers[i] = (((pfx << (ix.part_bases << 1)) | (uint64_t)lo) << ix.key_bits) | rem;
         vals[i] = lm_unpack_seed_val(pv, ix.g_bg[lm_packed_val_genome(pv, ix.pos_bits)], ix.pos_bits, (int)(md & 1));
     }
+}
+
+// The seeds [s0, s1) of the image - main seeds numbered as md_off counts them (FLAT = false) or outliers as out_off does
+// (FLAT = true) - in the staging form SeedPacker::count / place consume: (mask, k-mer, value in the reference's layout) at
+// i - s0.  [l0, l1) are the lists that hold them (sw_piece_lists).  The lanes run over the output seeds, so the packed reads
+// and the three output streams of a wavefront are contiguous: 18 B written per seed, the bit fields read once.  A tile of
+// blockDim.x seeds finds its first and last list and the partitions of its first and last seed once (uniform searches:
+// scalar loads); a lane searches between those brackets only (lm_seed_walk.h), which is a handful of partitions wherever
+// lists are longer than a tile.  The outlier lists are flat pairs: a copy with the mask id beside it.
+template <bool FLAT>
+__global__ __launch_bounds__(256) void k_sp_dump_range(DevIndexView ix, int64_t l0, int64_t l1, int64_t s0, int64_t s1,
+                                                        uint16_t *__restrict__ s_mask, uint64_t *__restrict__ s_kmer,
+                                                        uint64_t *__restrict__ s_val) {
+    const int64_t *__restrict__ off = FLAT ? ix.out_off : ix.md_off;
+    const int P = ix.P1 - 1;
+    const int val_bits = ix.gid_bits + ix.pos_bits + 1;
+    for (int64_t t0 = s0 + (int64_t)blockIdx.x * blockDim.x; t0 < s1; t0 += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t t1 = (t0 + (int64_t)blockDim.x < s1 ? t0 + (int64_t)blockDim.x : s1) - 1;
+        int64_t lf, ll;
+        sw_tile_lists(off, l0, l1, t0, t1, &lf, &ll);
+        int pf = 0, pl = P - 1;
+        if (!FLAT) {
+            pf = (int)sw_last_le(ix.part_tab + lf * ix.P1, 0, P - 1, t0 - off[lf]);
+            pl = (int)sw_last_le(ix.part_tab + ll * ix.P1, lf == ll ? pf : 0, P - 1, t1 - off[ll]);
+        }
+        const int64_t i = t0 + threadIdx.x;
+        if (i > t1) continue;
+        const int64_t md = sw_last_le(off, lf, ll, i), o = i - s0;
+        s_mask[o] = (uint16_t)(md >> 1);
+        if (FLAT) {
+            s_kmer[o] = ix.out_kmers[i];
+            s_val[o] = ix.out_vals[i];
+        } else {
+            const int part = sw_partition(ix.part_tab + md * ix.P1, P, i - off[md], md == lf, pf, md == ll, pl);
+            const uint64_t pfx = ix.masks[md >> 1] >> ((ix.K - ix.mask_prefix) << 1);
+            const uint64_t rem = lm_bits_get(ix.pk_keys, i, ix.key_bits);
+            const uint64_t pv = lm_bits_get(ix.pk_vals, i, val_bits);
+            s_kmer[o] = (((pfx << (ix.part_bases << 1)) | (uint64_t)part) << ix.key_bits) | rem;
+            s_val[o] = lm_unpack_seed_val(pv, ix.g_bg[lm_packed_val_genome(pv, ix.pos_bits)], ix.pos_bits, (int)(md & 1));
+        }
+    }
+}
+
+void sp_dump_range(const lm_index *src, hipStream_t st, const std::vector<int64_t> &off, bool flat, int64_t s0, int64_t s1,
+                   uint16_t *s_mask, uint64_t *s_kmer, uint64_t *s_val) {
+    if (s1 <= s0) return;
+    const int64_t nmd = (int64_t)off.size() - 1;
+    if (s0 < 0 || s1 > off[(size_t)nmd]) throw HipError("seed image: a decode piece outside the image");
+    int64_t l0, l1;
+    sw_piece_lists(off.data(), nmd, s0, s1, &l0, &l1);
+    // (a bandwidth kernel: at most 8 workgroups per CU, the rest of the piece by grid stride)
+    const unsigned grid = (unsigned)std::min<int64_t>((s1 - s0 + 255) / 256, 2048);
+    if (flat)
+        hipLaunchKernelGGL(k_sp_dump_range<true>, dim3(grid), dim3(256), 0, st, src->view, l0, l1, s0, s1, s_mask, s_kmer, s_val);
+    else
+        hipLaunchKernelGGL(k_sp_dump_range<false>, dim3(grid), dim3(256), 0, st, src->view, l0, l1, s0, s1, s_mask, s_kmer, s_val);
+    HIPCHK(hipGetLastError());
 }
 
 static int sp_grid(int64_t n, int block = 256) {
