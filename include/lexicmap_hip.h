@@ -85,7 +85,11 @@ lm_status lm_index_open(const char *dir, const lm_options *opt, int device, lm_i
 /* Synthetic genome set + seed index generated directly in HBM (benchmark input; nothing in the reference corresponds to
  * it — an index of real genomes is built with lm_index_builder_* below).  Genome g belongs to family g % families; genomes >= families are
  * mutated copies (substitution rate U(0,max_div), indel shifts at a tenth of that) of the family ancestor.  Honors
- * opt->shard_rank/shard_count.  See lexicmap_amd/csrc/lm_builder.hip for what is exact and what is simplified. */
+ * opt->shard_rank/shard_count.  The seeds come from the pipeline lm_index_builder_* uses (one set of kernels):
+ * captures, desert seeds and reversed seeds are the reference's for these genomes, including - for genomes too short to
+ * contain every p-base mask prefix, below about 100 kb with 20 000 masks - the rule that a mask without a k-mer of its prefix
+ * captures the argmin over all k-mers; earlier builds left such masks without a capture.  k must be 31, masks in
+ * [4, 65535] and at most 2 * 4^p (p = floor(log4 masks)), max_desert and seed_dist >= 1: LM_ERR_ARG otherwise. */
 typedef struct lm_synth_spec {
     int32_t k;            /* 31 */
     int32_t masks;        /* 20000 (index.go:560) */

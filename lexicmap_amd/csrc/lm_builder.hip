@@ -1,13 +1,18 @@
-// lm_builder.hip — the seed index built on the GPU.  Two builders: the synthetic genome set + index generated directly in
-// HBM (bench / large-scale test input, first half of this file) and the builder for caller-supplied genomes
-// (lm_index_builder_*, second half).
-//
-// The synthetic builder exists because the benchmark configurations (10k x 5 Mb genomes and up) cannot be built by any CPU
-// tool on a fresh box within minutes, and nothing persists on the GPU box.  What it produces has the same structure as a reference-built index (lib-index-build.go):
-//   * genomes: procedural i.i.d. ACGT ancestors per family; members are substituted (rate U(0,max_div)) and
-//     indel-shifted copies; single contig; stored 2-bit MSB-first like genome/genome.go:1471-1508
-//   * normal seeds: EXACT LexicHash capture per genome — for every mask the argmin of mask^kmer over both strands, all
-//     occurrences, low-complexity captures dropped (lib-index-build.go:1028-1046)
+// lm_builder.hip — the seed index built on the GPU.  One seed pipeline with two front ends:
+//   * lm_index_build_synthetic(_ex): a synthetic genome set generated directly in HBM (bench / large-scale test input).  It
+//     exists because the benchmark configurations (10k x 5 Mb genomes and up) cannot be built by any CPU tool on a fresh box
+//     within minutes, and nothing persists on the GPU box.  Genomes: procedural i.i.d. ACGT ancestors per family; members
+//     are substituted (rate U(0,max_div)) and indel-shifted copies; single contig; stored 2-bit MSB-first like
+//     genome/genome.go:1471-1508.  A sharded set is numbered without a table: local genome l is genome l * shard_count + rank.
+//   * lm_index_builder_*: caller-supplied genomes of any length, with several contigs and skip regions, added one by one
+//     (planner of records, spacers, skip regions, keys, shards: lm_build_plan.h), or added to a resident index (_extend).
+// A front end validates its settings, sets up the header and the masks (builder_header), puts the 2-bit records into one
+// store and describes them in HostIndex::genomes; build_seed_index does the rest for both, with the same kernels.  What it
+// produces has the same structure as a reference-built index (lib-index-build.go):
+//   * normal seeds: EXACT LexicHash capture per record — for every mask the argmin of mask^kmer over both strands, all
+//     occurrences, low-complexity captures dropped (lib-index-build.go:1028-1046); k-mers that overlap a skip region are
+//     left out, and a mask whose p-base prefix no k-mer of the record shares captures the argmin over ALL k-mers
+//     (lexichash MaskKnownDistinctPrefixes(..., checkShorterPrefix = true), lib-index-build.go:1028)
 //   * seed-desert filling as the reference does it (lib-index-build.go:1094-1407): every gap >= max_desert between
 //     neighbouring seeds is filled every seed_dist bases with the nearest non-low-complexity k-mer (scan 25 up-, then 24
 //     downstream, + strand before - strand) that is the capture of a mask when the window [pre - 1000, pos + 1000 + k)
@@ -22,6 +27,7 @@
 
 #include "lm_internal.h"
 #include "lm_prims.h"
+#include "lm_build_plan.h"
 
 namespace lm {
 
@@ -128,184 +134,6 @@ struct MaskTab {
     int K, p, M;
 };
 
-// pass A: per genome of the chunk, argmin hash per mask
-__global__ void k_cap_argmin(SynthDev sp, MaskTab mt, const uint8_t *__restrict__ gbits, int64_t l0, int nchunk,
-                             unsigned long long *__restrict__ hashes) {
-    int64_t npos = (int64_t)sp.genome_len - mt.K + 1;
-    int64_t total = (int64_t)nchunk * npos;
-    int shift = (mt.K - mt.p) << 1;
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        int c = (int)(t / npos);
-        int64_t pos = t % npos;
-        const uint8_t *gb = gbits + (l0 + c) * sp.gbytes;
-        uint64_t fwd = packed_kmer(gb, pos, mt.K);
-        uint64_t rc = lm_revcomp(fwd, mt.K);
-        unsigned long long *hs = hashes + (int64_t)c * mt.M;
-        for (int s = 0; s < 2; s++) {
-            uint64_t x = s ? rc : fwd;
-            uint64_t pf = x >> shift;
-            for (int j = mt.pfx_first[pf]; j < mt.pfx_first[pf + 1]; j++) {
-                unsigned long long h = mt.masks[j] ^ x;
-                if (h < hs[j]) atomicMin(&hs[j], h);
-            }
-        }
-    }
-}
-
-// pass B: emit every occurrence of every captured k-mer
-__global__ void k_cap_emit(SynthDev sp, MaskTab mt, const uint8_t *__restrict__ gbits, int64_t l0, int nchunk,
-                           const unsigned long long *__restrict__ hashes, uint16_t *__restrict__ s_mask,
-                           uint64_t *__restrict__ s_kmer, uint64_t *__restrict__ s_val, unsigned long long *__restrict__ counter,
-                           unsigned long long cap, uint64_t *__restrict__ pos_keys, unsigned long long *__restrict__ pos_counter,
-                           unsigned long long pos_cap) {
-    int64_t npos = (int64_t)sp.genome_len - mt.K + 1;
-    int64_t total = (int64_t)nchunk * npos;
-    int shift = (mt.K - mt.p) << 1;
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        int c = (int)(t / npos);
-        int64_t pos = t % npos;
-        const uint8_t *gb = gbits + (l0 + c) * sp.gbytes;
-        uint64_t fwd = packed_kmer(gb, pos, mt.K);
-        uint64_t rc = lm_revcomp(fwd, mt.K);
-        const unsigned long long *hs = hashes + (int64_t)c * mt.M;
-        int64_t g = global_genome(sp, l0 + c);
-        uint64_t bg = ((uint64_t)(g / 5000) << 17) | (uint64_t)(g % 5000);
-        for (int s = 0; s < 2; s++) {
-            uint64_t x = s ? rc : fwd;
-            uint64_t pf = x >> shift;
-            bool lc_known = false, lc = false;
-            for (int j = mt.pfx_first[pf]; j < mt.pfx_first[pf + 1]; j++) {
-                if ((mt.masks[j] ^ x) != hs[j]) continue;
-                if (!lc_known) {
-                    lc = x == 0 || lm_low_complexity(x, mt.K);
-                    lc_known = true;
-                }
-                if (lc) continue;
-                unsigned long long o = atomicAdd(counter, 1ull);
-                if (o < cap) {
-                    s_mask[o] = (uint16_t)j;
-                    s_kmer[o] = x;
-                    s_val[o] = (bg << 30) | ((uint64_t)pos << 2) | ((uint64_t)s << 1);
-                }
-                unsigned long long po = atomicAdd(pos_counter, 1ull);
-                if (po < pos_cap) pos_keys[po] = ((uint64_t)c << 32) | ((uint64_t)pos << 1) | (uint64_t)s;
-            }
-        }
-    }
-}
-
-// LexicHash capture of one genome by one workgroup, both passes in one launch: the per-mask minima live in LDS
-// (M x 8 B = 160 KB for the default 20000 masks: the whole LDS of a CU) instead of a global table hammered with atomics.
-// Masks of a p-base prefix are found without a table in memory: in a lexicmap mask set every prefix has one mask and
-// some have two (docs/content/usage/utils/masks.md:69-110), so first(pf) = pf + #doubled prefixes below pf: a 4^p-bit
-// map + per-word counts (2.5 KB).  Phase 1: ds_min_u64 of mask^kmer; phase 2: every k-mer equal to its mask's minimum is
-// emitted (all occurrences, lib-index-build.go:1028-1046), low-complexity captures dropped.
-__global__ __launch_bounds__(1024) void k_capture_lds(SynthDev sp, MaskTab mt, const uint8_t *__restrict__ gbits, int64_t l0,
-                                                      const uint64_t *__restrict__ dbl_map, const uint32_t *__restrict__ dbl_cnt,
-                                                      uint16_t *__restrict__ s_mask, uint64_t *__restrict__ s_kmer,
-                                                      uint64_t *__restrict__ s_val, unsigned long long *__restrict__ counter,
-                                                      unsigned long long cap, uint64_t *__restrict__ pos_keys,
-                                                      unsigned long long *__restrict__ pos_counter, unsigned long long pos_cap) {
-    extern __shared__ unsigned long long lds_dyn[];
-    unsigned long long *hs = lds_dyn;                                   // [M]
-    const int nw = ((1 << (2 * mt.p)) + 63) >> 6;
-    unsigned long long *bm = hs + mt.M;                                  // [nw]
-    uint32_t *bc = (uint32_t *)(bm + nw);                                // [nw]
-    const int c = blockIdx.x;
-    const uint8_t *gb = gbits + (l0 + c) * sp.gbytes;
-    const int64_t npos = (int64_t)sp.genome_len - mt.K + 1;
-    const int shift = (mt.K - mt.p) << 1;
-    for (int i = threadIdx.x; i < mt.M; i += blockDim.x) hs[i] = ~0ull;
-    for (int i = threadIdx.x; i < nw; i += blockDim.x) {
-        bm[i] = dbl_map[i];
-        bc[i] = dbl_cnt[i];
-    }
-    __syncthreads();
-    for (int64_t pos = threadIdx.x; pos < npos; pos += blockDim.x) {
-        const uint64_t fwd = packed_kmer(gb, pos, mt.K);
-        const uint64_t rc = lm_revcomp(fwd, mt.K);
-#pragma unroll
-        for (int s = 0; s < 2; s++) {
-            const uint64_t x = s ? rc : fwd;
-            const uint32_t pf = (uint32_t)(x >> shift);
-            const unsigned long long w = bm[pf >> 6];
-            const int j0 = (int)(pf + bc[pf >> 6] + (uint32_t)__popcll(w & ((1ull << (pf & 63)) - 1)));
-            const int nj = 1 + (int)((w >> (pf & 63)) & 1ull);
-            for (int j = j0; j < j0 + nj; j++) {
-                const unsigned long long h = mt.masks[j] ^ x;
-                if (h < hs[j]) atomicMin(&hs[j], h);
-            }
-        }
-    }
-    __syncthreads();
-    const int64_t g = global_genome(sp, l0 + c);
-    const uint64_t bg = ((uint64_t)(g / 5000) << 17) | (uint64_t)(g % 5000);
-    // phase 2a counts this thread's captures, the workgroup reserves ONE contiguous range of the staging arrays for the
-    // genome (a per-capture atomic on the shared counter costs more than the whole sweep), phase 2b writes
-    uint32_t *wsum = bc + nw; // [16] wave totals
-    __shared__ unsigned long long base_seed, base_pos;
-    uint32_t mine = 0;
-    for (int sweep = 0; sweep < 2; sweep++) {
-        unsigned long long o = 0, po = 0;
-        if (sweep == 1) {
-            uint32_t incl = mine;
-            const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t v = __shfl_up(incl, d);
-                if (lane >= d) incl += v;
-            }
-            if (lane == 63) wsum[wave] = incl;
-            __syncthreads();
-            uint32_t before = 0, all = 0;
-            for (int w2 = 0; w2 < (int)(blockDim.x >> 6); w2++) {
-                if (w2 < wave) before += wsum[w2];
-                all += wsum[w2];
-            }
-            if (threadIdx.x == 0) {
-                base_seed = atomicAdd(counter, (unsigned long long)all);
-                base_pos = atomicAdd(pos_counter, (unsigned long long)all);
-            }
-            __syncthreads();
-            o = base_seed + before + (incl - mine);
-            po = base_pos + before + (incl - mine);
-        }
-        for (int64_t pos = threadIdx.x; pos < npos; pos += blockDim.x) {
-            const uint64_t fwd = packed_kmer(gb, pos, mt.K);
-            const uint64_t rc = lm_revcomp(fwd, mt.K);
-#pragma unroll
-            for (int s = 0; s < 2; s++) {
-                const uint64_t x = s ? rc : fwd;
-                const uint32_t pf = (uint32_t)(x >> shift);
-                const unsigned long long w = bm[pf >> 6];
-                const int j0 = (int)(pf + bc[pf >> 6] + (uint32_t)__popcll(w & ((1ull << (pf & 63)) - 1)));
-                const int nj = 1 + (int)((w >> (pf & 63)) & 1ull);
-                for (int j = j0; j < j0 + nj; j++) {
-                    if ((mt.masks[j] ^ x) != hs[j]) continue;
-                    if (x == 0 || lm_low_complexity(x, mt.K)) continue;
-                    if (sweep == 0) {
-                        mine++;
-                        continue;
-                    }
-                    if (o < cap) {
-                        s_mask[o] = (uint16_t)j;
-                        s_kmer[o] = x;
-                        s_val[o] = (bg << 30) | ((uint64_t)pos << 2) | ((uint64_t)s << 1);
-                    }
-                    if (po < pos_cap) pos_keys[po] = ((uint64_t)c << 32) | ((uint64_t)pos << 1) | (uint64_t)s;
-                    o++;
-                    po++;
-                }
-            }
-        }
-    }
-}
-
-__global__ void k_pseudo_pos(int nchunk, int32_t last_pos, uint64_t *__restrict__ pos_keys, unsigned long long base) {
-    int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < nchunk) pos_keys[base + c] = ((uint64_t)c << 32) | ((uint64_t)(uint32_t)last_pos << 1) | 1ull; // sorts last
-}
-
 __device__ __forceinline__ int closest_mask(const MaskTab &mt, uint64_t x) {
     uint64_t pf = x >> ((mt.K - mt.p) << 1);
     int minj = -1;
@@ -320,13 +148,6 @@ __device__ __forceinline__ int closest_mask(const MaskTab &mt, uint64_t x) {
     return minj;
 }
 
-// Desert filling, lib-index-build.go:1094-1407, as the reference does it: for every pair of neighbouring seeds at least
-// max_desert apart, walk from pre + seed_dist in steps of seed_dist; at each step scan seed_pos_r positions upstream, then
-// downstream, for a non-low-complexity k-mer (+ strand before - strand) that IS THE CAPTURE OF SOME MASK WHEN THE WINDOW
-// [pre - 1000, pos + 1000 + k) ALONE IS MASKED (MaskKnownDistinctPrefixes(window, nil, false), :1191-1240), and store it
-// under that mask - the LAST (largest-index) mask that captures it.  A wavefront takes 64 seed pairs, finds the deserts
-// among them and walks them one after the other; the capture test of a candidate is a sweep of the window by the 64 lanes
-// (is any window k-mer of either strand with the same p-base prefix closer to the mask?).
 // the p-base prefixes (p <= 16) of the k-mer at `pos` and of its reverse complement, from one 32-base window of the 2-bit
 // genome: all the sweep below needs for the ~16 000 : 1 window k-mers that do not share the candidate's prefix
 __device__ __forceinline__ void kmer_prefixes(const uint8_t *gb, int64_t pos, int K, int p, uint32_t *fwd, uint32_t *rc) {
@@ -341,6 +162,8 @@ __device__ __forceinline__ void kmer_prefixes(const uint8_t *gb, int64_t pos, in
     y = ((y >> 1) & 0x55555555u) | ((y & 0x55555555u) << 1);                       // ... and put the base pairs back in order
     *rc = y >> (32 - 2 * p);
 }
+// the capture test of a desert candidate x (k_desert_fill_g), by the 64 lanes of a wavefront: the last mask for which x
+// attains the minimum over the nk k-mers of the window from wstart, or -1
 __device__ __forceinline__ int desert_capturing_mask(const MaskTab &mt, const uint8_t *gb, int64_t wstart, int nk, uint64_t x,
                                                      int lane) {
     const int shift = (mt.K - mt.p) << 1;
@@ -367,100 +190,6 @@ __device__ __forceinline__ int desert_capturing_mask(const MaskTab &mt, const ui
         if (!((beaten >> (j - j0)) & 1u)) im = j; // x attains the window's minimum for mask j; the last such mask is recorded
     return im;
 }
-__global__ __launch_bounds__(256) void k_desert_fill(SynthDev sp, MaskTab mt, const uint8_t *__restrict__ gbits, int64_t l0,
-                                                      const uint64_t *__restrict__ pos_keys, int64_t npk, int max_desert,
-                                                      int seed_dist, uint16_t *__restrict__ s_mask,
-                                                      uint64_t *__restrict__ s_kmer, uint64_t *__restrict__ s_val,
-                                                      unsigned long long *__restrict__ counter, unsigned long long cap) {
-    const int seed_pos_r = seed_dist / 2;
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
-    for (int64_t base = wave * 64; base < npk; base += nwaves * 64) {
-        const int64_t t = base + lane;
-        int c = 0, pos = 0, pre = 0;
-        bool isd = false;
-        if (t < npk) {
-            const uint64_t key = pos_keys[t];
-            c = (int)(key >> 32);
-            pos = (int)((key & 0xffffffffu) >> 1);
-            if (t > 0 && (int)(pos_keys[t - 1] >> 32) == c) pre = (int)((pos_keys[t - 1] & 0xffffffffu) >> 1);
-            isd = pos - pre >= max_desert;
-        }
-        uint64_t todo = __ballot(isd);
-        while (todo) {
-            const int src = __ffsll((long long)todo) - 1;
-            todo &= todo - 1;
-            const int gc = __builtin_amdgcn_readfirstlane(__shfl(c, src, 64));
-            const int gpos = __builtin_amdgcn_readfirstlane(__shfl(pos, src, 64));
-            const int gpre = __builtin_amdgcn_readfirstlane(__shfl(pre, src, 64));
-            const uint8_t *gb = gbits + (l0 + gc) * sp.gbytes;
-            const int64_t g = global_genome(sp, l0 + gc);
-            const uint64_t bg = ((uint64_t)(g / 5000) << 17) | (uint64_t)(g % 5000);
-            // the window that is masked on its own (:1150-1190)
-            int wstart = gpre - 1000;
-            if (wstart < 0) wstart = 0;
-            int wend = gpos + 1000 + mt.K;
-            if (wend > sp.genome_len) wend = sp.genome_len;
-            const int nk = wend - wstart - mt.K + 1; // k-mers of the window
-            auto try_at = [&](int at, uint64_t *kmer, int *strand, int *im) { // the candidate at genome position `at`
-                const int rel = at - wstart;
-                if (rel < 0 || rel >= nk) return false;
-                const uint64_t f = packed_kmer(gb, at, mt.K);
-                if (f != 0 && !lm_low_complexity(f, mt.K)) {
-                    const int m = desert_capturing_mask(mt, gb, wstart, nk, f, lane);
-                    if (m >= 0) {
-                        *kmer = f;
-                        *strand = 0;
-                        *im = m;
-                        return true;
-                    }
-                }
-                const uint64_t r = lm_revcomp(f, mt.K);
-                if (r != 0 && !lm_low_complexity(r, mt.K)) {
-                    const int m = desert_capturing_mask(mt, gb, wstart, nk, r, lane);
-                    if (m >= 0) {
-                        *kmer = r;
-                        *strand = 1;
-                        *im = m;
-                        return true;
-                    }
-                }
-                return false;
-            };
-            int j = gpre + seed_dist;
-            while (j < gpos) {
-                const int start_dn = j + 1, end_up = j - seed_pos_r;
-                bool ok = false;
-                uint64_t kmer = 0;
-                int strand = 0, im = -1, at = j;
-                for (; at > end_up; at--)
-                    if (try_at(at, &kmer, &strand, &im)) {
-                        ok = true;
-                        break;
-                    }
-                if (!ok) {
-                    if (start_dn >= gpos) break;
-                    int end_dn = start_dn + seed_pos_r;
-                    if (end_dn >= gpos) end_dn = gpos - 1;
-                    for (at = start_dn; at < end_dn; at++)
-                        if (try_at(at, &kmer, &strand, &im)) {
-                            ok = true;
-                            break;
-                        }
-                }
-                if (ok && lane == 0) {
-                    const unsigned long long o = atomicAdd(counter, 1ull);
-                    if (o < cap) {
-                        s_mask[o] = (uint16_t)im;
-                        s_kmer[o] = kmer;
-                        s_val[o] = (bg << 30) | ((uint64_t)at << 2) | ((uint64_t)strand << 1);
-                    }
-                }
-                j = at + seed_dist;
-            }
-        }
-    }
-}
 
 // reversed copies of seeds [from, to)
 __global__ void k_reverse_seeds(MaskTab mt, unsigned long long from, unsigned long long to, uint16_t *__restrict__ s_mask,
@@ -479,10 +208,6 @@ __global__ void k_reverse_seeds(MaskTab mt, unsigned long long from, unsigned lo
     }
 }
 
-__global__ void k_fill_u64(unsigned long long *p, int64_t n, unsigned long long v) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = v;
-}
-
 __global__ void k_fetch_bases(const uint8_t *__restrict__ gb, int64_t start, int64_t len, uint8_t *__restrict__ out) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < len; i += (int64_t)gridDim.x * blockDim.x) {
         int64_t p = start + i;
@@ -497,10 +222,12 @@ static int gridn(int64_t n, int block = 256) {
     return (int)g;
 }
 
+static int mask_prefix_of(int M) { return std::max(1, (int)(std::log2((double)M) / 2)); }
+
 // host-side mask set with the structure of lexicmap masks (docs/content/usage/utils/masks.md:69-110): all p-prefixes
 // present, M-4^p extra masks on distinct prefixes differing from their twin at base p+1, sorted.
 static void gen_masks(int k, int M, uint64_t seed, std::vector<uint64_t> &out) {
-    int p = std::max(1, (int)(std::log2((double)M) / 2));
+    int p = mask_prefix_of(M);
     int64_t np = (int64_t)1 << (2 * p);
     int lowbits = (k - p) << 1;
     uint64_t lowmask = (1ull << lowbits) - 1;
@@ -531,347 +258,9 @@ static void gen_masks(int k, int M, uint64_t seed, std::vector<uint64_t> &out) {
     std::sort(out.begin(), out.end());
 }
 
-} // namespace lm
-
-extern "C" {
-
-lm_status lm_index_build_synthetic(const lm_synth_spec *spec, const lm_options *opt, int device, lm_index **out) {
-    return lm_index_build_synthetic_ex(spec, opt, nullptr, device, out);
-}
-lm_status lm_index_build_synthetic_ex(const lm_synth_spec *spec, const lm_options *opt, const lm_residency *res, int device, lm_index **out) {
-    *out = nullptr;
-    lm_res_request rq;
-    {
-        const lm_status rs = lm_res_resolve(res, rq, g_open_error);
-        if (rs != LM_OK) return rs;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
-        g_open_error = "no HIP device available (this library has no CPU path)";
-        return LM_ERR_NO_DEVICE;
-    }
-    if (spec->k != 31 || spec->masks < 4 || spec->masks > 65535 || spec->genome_len < 64 || spec->genomes < 1 ||
-        spec->genome_len >= (1 << 28) || spec->families < 1) {
-        g_open_error = "lm_index_build_synthetic: unsupported spec (k must be 31, masks in [4,65535])";
-        return LM_ERR_ARG;
-    }
-    lm_index *ix = new lm_index();
-    try {
-        ix->opt = *opt;
-        ix->device = device;
-        HIPCHK(hipSetDevice(device));
-        HIPCHK(hipStreamCreate(&ix->st));
-        HostIndex &h = ix->host;
-        const int K = spec->k, M = spec->masks;
-        h.k = K;
-        h.M = M;
-        h.main_version = 3;
-        h.minor_version = 5;
-        h.synthetic = true;
-        h.synth_genome_len = spec->genome_len;
-        h.synth_genomes = spec->genomes;
-        h.mask_prefix = std::max(1, (int)(std::log2((double)M) / 2));
-        h.anchor_prefix = 6;
-        h.contig_interval = 1000;
-        h.shard_rank = opt->shard_count > 1 ? opt->shard_rank : 0;
-        h.shard_count = opt->shard_count > 1 ? opt->shard_count : 1;
-        h.total_bases = opt->total_bases_override > 0 ? opt->total_bases_override : spec->genomes * (int64_t)spec->genome_len;
-        gen_masks(K, M, (uint64_t)spec->mask_seed, h.masks);
-        const int p = h.mask_prefix;
-        std::vector<int32_t> pfx((size_t)(1ull << (2 * p)) + 1, 0);
-        for (int i = 0; i < M; i++) pfx[(size_t)(h.masks[i] >> ((K - p) << 1)) + 1]++;
-        for (size_t i = 1; i < pfx.size(); i++) pfx[i] += pfx[i - 1];
-        {
-            if (opt->min_prefix > K || opt->min_prefix < p + h.anchor_prefix) {
-                g_open_error = "MinPrefix out of range for this index";
-                delete ix;
-                return LM_ERR_OPTION;
-            }
-        }
-        // local genomes
-        int64_t nlocal = 0;
-        for (int64_t g = 0; g < spec->genomes; g++)
-            if ((int)(g % h.shard_count) == h.shard_rank) nlocal++;
-        SynthDev sp;
-        sp.seed = (uint64_t)spec->seed;
-        sp.genomes = spec->genomes;
-        sp.genome_len = spec->genome_len;
-        sp.families = (int32_t)std::min<int64_t>(spec->families, spec->genomes);
-        sp.max_div = spec->max_div;
-        sp.shard_rank = h.shard_rank;
-        sp.shard_count = h.shard_count;
-        sp.nlocal = nlocal;
-        sp.nblk = (spec->genome_len + 511) >> 9;
-        sp.gbytes = ((((int64_t)spec->genome_len + 3) >> 2) + 16 + 7) & ~(int64_t)7;
-        h.genome_batches = (int)((spec->genomes + 4999) / 5000);
-        h.batch_first.assign(h.genome_batches + 1, 0);
-        for (int b = 0; b <= h.genome_batches; b++) h.batch_first[b] = std::min<int64_t>((int64_t)b * 5000, spec->genomes);
-
-        auto copy_up = [&](auto &dbuf, const auto &vec) {
-            dbuf.ensure(std::max<size_t>(vec.size(), 1));
-            HIPCHK(hipMemcpyAsync(dbuf.p, vec.data(), vec.size() * sizeof(vec[0]), hipMemcpyHostToDevice, ix->st));
-        };
-        copy_up(ix->d_masks, h.masks);
-        copy_up(ix->d_pfx_first, pfx);
-        copy_up(ix->d_batch_first, h.batch_first);
-        // genomes
-        ix->d_gbits.alloc_exact((size_t)(nlocal * sp.gbytes) + 64);
-        HIPCHK(hipMemsetAsync(ix->d_gbits.p, 0, (size_t)(nlocal * sp.gbytes) + 64, ix->st));
-        DBuf<int16_t> shifts;
-        shifts.ensure((size_t)(nlocal * sp.nblk) + 1);
-        hipLaunchKernelGGL(k_synth_shifts, dim3(gridn(nlocal, 64)), dim3(64), 0, ix->st, sp, shifts.p);
-        hipLaunchKernelGGL(k_synth_genomes, dim3(gridn(nlocal * (((int64_t)spec->genome_len + 3) >> 2))), dim3(256), 0, ix->st,
-                           sp, shifts.p, ix->d_gbits.p);
-        bsync(ix);
-        shifts.release();
-        MaskTab mt{ix->d_masks.p, ix->d_pfx_first.p, K, p, M};
-        // genome tables + host metadata
-        std::vector<int64_t> goff(nlocal);
-        std::vector<int32_t> glen(nlocal, spec->genome_len);
-        std::vector<uint64_t> gbg(nlocal);
-        h.genomes.resize(nlocal);
-        for (int64_t l = 0; l < nlocal; l++) {
-            int64_t g = h.shard_count > 1 ? l * h.shard_count + h.shard_rank : l;
-            HostGenome &G = h.genomes[l];
-            G.bg = ((uint64_t)(g / 5000) << 17) | (uint64_t)(g % 5000);
-            G.global = g;
-            char nm[64];
-            snprintf(nm, sizeof nm, "SYN_%09lld.1", (long long)g);
-            G.id = nm;
-            G.genome_size = spec->genome_len;
-            G.len = spec->genome_len;
-            G.nseqs = 1;
-            G.seq_sizes = {spec->genome_len};
-            snprintf(nm, sizeof nm, "syn%09lld_c1", (long long)g);
-            G.seq_ids = {std::string(nm)};
-            G.bits_off = l * sp.gbytes;
-            goff[l] = G.bits_off;
-            gbg[l] = G.bg;
-            ix->bg2local[G.bg] = (int)l;
-        }
-        copy_up(ix->d_g_off, goff);
-        copy_up(ix->d_g_len, glen);
-        copy_up(ix->d_g_bg, gbg);
-        lm_fill_gap_lut(ix); // same table as lm_index_open (lib-chaining.go:662-667)
-        bsync(ix);
-        DevIndexView &v = ix->view;
-        v.K = K;
-        v.M = M;
-        v.mask_prefix = p;
-        v.masks = ix->d_masks.p;
-        v.pfx_first = ix->d_pfx_first.p;
-        v.g_bg = ix->d_g_bg.p;
-        v.gbits = ix->d_gbits.p;
-        v.g_off = ix->d_g_off.p;
-        v.g_len = ix->d_g_len.p;
-        v.batch_first = ix->d_batch_first.p;
-        v.nbatches = h.genome_batches;
-        v.ngenomes = nlocal;
-        v.shard_rank = h.shard_rank;
-        v.shard_count = h.shard_count;
-
-        // ---- seeds: generated per chunk of genomes into a staging buffer and shown to the packer, twice (count, place):
-        // the unpacked seeds of the whole set never exist (they would not fit beside the packed image at BASELINE configs 3-5)
-        const bool dbg = getenv("LM_DEBUG") != nullptr;
-        // capture in LDS when the per-mask minima fit a CU's LDS and the mask set has the lexicmap structure (every
-        // p-base prefix once or twice); otherwise minima in a global table
-        const int npfx = 1 << (2 * p), nwords = (npfx + 63) >> 6;
-        bool lds_capture = true;
-        std::vector<uint64_t> dmap(nwords, 0);
-        std::vector<uint32_t> dcnt(nwords, 0);
-        for (int f = 0; f < npfx; f++) {
-            const int c = pfx[f + 1] - pfx[f];
-            if (c < 1 || c > 2) lds_capture = false;
-            if (c == 2) dmap[f >> 6] |= 1ull << (f & 63);
-        }
-        for (int w = 1; w < nwords; w++) dcnt[w] = dcnt[w - 1] + (uint32_t)__builtin_popcountll(dmap[w - 1]);
-        const size_t lds_bytes = (size_t)M * 8 + (size_t)nwords * 12 + 64;
-        if (lds_bytes > 160 * 1024) lds_capture = false;
-        DBuf<uint64_t> dbl_map;
-        DBuf<uint32_t> dbl_cnt;
-        copy_up(dbl_map, dmap);
-        copy_up(dbl_cnt, dcnt);
-        if (lds_capture && lds_bytes > 64 * 1024)
-            HIPCHK(hipFuncSetAttribute((const void *)k_capture_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        const int CH = (int)std::min<int64_t>(nlocal, lds_capture ? 2048 : std::max<int64_t>(1, (int64_t)(192ll << 20) / ((int64_t)M * 8)));
-        double per_genome = 2.0 * (1.45 * M + (double)spec->genome_len / 42.0) + 1024;
-        unsigned long long cap = (unsigned long long)(per_genome * (double)CH) + 65536;
-        DBuf<uint16_t> s_mask;
-        DBuf<uint64_t> s_kmer, s_val;
-        s_mask.alloc_exact(cap);
-        s_kmer.alloc_exact(cap);
-        s_val.alloc_exact(cap);
-        DBuf<unsigned long long> counters;
-        counters.ensure(8);
-        DBuf<unsigned long long> hashes;
-        hashes.alloc_exact(lds_capture ? 1 : (size_t)CH * M);
-        unsigned long long pos_cap = (unsigned long long)((1.45 * M + 64) * CH) + CH + 64;
-        DBuf<uint64_t> pos_keys, pos_keys2;
-        pos_keys.alloc_exact(pos_cap);
-        pos_keys2.alloc_exact(pos_cap);
-        const int64_t npos = (int64_t)spec->genome_len - K + 1;
-        SeedPacker packer;
-        packer.begin(ix, nlocal, spec->genome_len);
-        double t_cap = 0, t_desert = 0, t_pack = 0;
-        for (int pass = 0; pass < 2; pass++) {
-            for (int64_t l0 = 0; l0 < nlocal; l0 += CH) {
-                int nch = (int)std::min<int64_t>(CH, nlocal - l0);
-                double ta = now_ms();
-                HIPCHK(hipMemsetAsync(counters.p, 0, 2 * sizeof(unsigned long long), ix->st));
-                if (lds_capture) {
-                    hipLaunchKernelGGL(k_capture_lds, dim3(nch), dim3(1024), lds_bytes, ix->st, sp, mt, ix->d_gbits.p, l0,
-                                       dbl_map.p, dbl_cnt.p, s_mask.p, s_kmer.p, s_val.p, counters.p, cap, pos_keys.p,
-                                       counters.p + 1, pos_cap - CH - 1);
-                } else {
-                    hipLaunchKernelGGL(k_fill_u64, dim3(gridn((int64_t)nch * M)), dim3(256), 0, ix->st, hashes.p,
-                                       (int64_t)nch * M, ~0ull);
-                    hipLaunchKernelGGL(k_cap_argmin, dim3(gridn((int64_t)nch * npos)), dim3(256), 0, ix->st, sp, mt,
-                                       ix->d_gbits.p, l0, nch, hashes.p);
-                    hipLaunchKernelGGL(k_cap_emit, dim3(gridn((int64_t)nch * npos)), dim3(256), 0, ix->st, sp, mt, ix->d_gbits.p,
-                                       l0, nch, hashes.p, s_mask.p, s_kmer.p, s_val.p, counters.p, cap, pos_keys.p,
-                                       counters.p + 1, pos_cap - CH - 1);
-                }
-                unsigned long long hc[2];
-                HIPCHK(hipMemcpyAsync(hc, counters.p, sizeof hc, hipMemcpyDeviceToHost, ix->st));
-                bsync(ix);
-                if (hc[0] >= cap || hc[1] >= pos_cap - CH - 1) throw HipError("synthetic builder: seed buffer too small");
-                double tb = now_ms();
-                unsigned long long npk = hc[1];
-                hipLaunchKernelGGL(k_pseudo_pos, dim3((nch + 63) / 64), dim3(64), 0, ix->st, nch, (int32_t)(spec->genome_len - K),
-                                   pos_keys.p, npk);
-                npk += nch;
-                prim_sort_keys(ix->st, ix->tmp, pos_keys.p, pos_keys2.p, (size_t)npk, 0, 64);
-                hipLaunchKernelGGL(k_desert_fill, dim3(gridn(((int64_t)npk + 63) / 64, 4)), dim3(256), 0, ix->st, sp, mt, ix->d_gbits.p, l0,
-                                   pos_keys2.p, (int64_t)npk, spec->max_desert, spec->seed_dist, s_mask.p, s_kmer.p, s_val.p,
-                                   counters.p, cap);
-                HIPCHK(hipMemcpyAsync(hc, counters.p, sizeof hc, hipMemcpyDeviceToHost, ix->st));
-                bsync(ix);
-                if (hc[0] >= cap) throw HipError("synthetic builder: seed buffer too small (desert)");
-                unsigned long long upto = hc[0];
-                hipLaunchKernelGGL(k_reverse_seeds, dim3(gridn((int64_t)upto)), dim3(256), 0, ix->st, mt, 0ull, upto, s_mask.p,
-                                   s_kmer.p, s_val.p, counters.p, cap);
-                HIPCHK(hipMemcpyAsync(hc, counters.p, sizeof hc, hipMemcpyDeviceToHost, ix->st));
-                bsync(ix);
-                if (hc[0] >= cap) throw HipError("synthetic builder: seed buffer too small (reversed)");
-                double tc = now_ms();
-                if (pass == 0)
-                    packer.count(s_mask.p, s_kmer.p, s_val.p, (int64_t)hc[0]);
-                else
-                    packer.place(s_mask.p, s_kmer.p, s_val.p, (int64_t)hc[0]);
-                bsync(ix);
-                t_cap += tb - ta;
-                t_desert += tc - tb;
-                t_pack += now_ms() - tc;
-            }
-            if (pass == 0) packer.end_count();
-            if (dbg)
-                fprintf(stderr, "[lm] builder pass %d: capture %.0f ms, desert+reverse %.0f ms, packer %.0f ms (cumulative)\n", pass,
-                        t_cap, t_desert, t_pack);
-        }
-        hashes.release();
-        pos_keys.release();
-        pos_keys2.release();
-        s_mask.release();
-        s_kmer.release();
-        s_val.release();
-        double tf = now_ms();
-        packer.finish();
-        if (dbg) fprintf(stderr, "[lm] builder: partition sort %.0f ms; %lld seeds (%lld outliers), %.2f B/seed\n", now_ms() - tf,
-                         (long long)ix->n_seeds, (long long)ix->n_seeds_outlier, (double)ix->seed_bytes / std::max<double>(1.0, (double)ix->n_seeds));
-        ix->tmp.release();
-        // ---- residency: the set is built in HBM as ever; the genomes beyond the budget then move to pinned host memory and the
-        // device store shrinks to the rest (a set that does not fit the device DURING the build is out of reach of this form)
-        ix->res.genomes_device = nlocal;
-        ix->res.genome_bytes_device = nlocal * sp.gbytes;
-        {
-            const int64_t nb = (((int64_t)spec->genome_len + 3) >> 2);
-            int64_t budget = rq.budget;
-            if (rq.mode == LM_GENOMES_AUTO && budget == 0) {
-                size_t fr = 0, tot = 0;
-                HIPCHK(hipMemGetInfo(&fr, &tot));
-                budget = lm_res_auto_budget((int64_t)fr + nlocal * sp.gbytes, 0); // (the store itself is part of what it may take)
-            }
-            // the builder's device slots are sp.gbytes wide (a little more padding than the loader's) and the budget is counted in
-            // those: the first `keep` genomes stay, the rest go to the host - the planner lays out the host side only
-            const int64_t keep = rq.mode == LM_GENOMES_DEVICE ? nlocal
-                                 : rq.mode == LM_GENOMES_HOST ? 0
-                                                              : std::min<int64_t>(nlocal, budget / sp.gbytes);
-            if (keep < nlocal) {
-                ResidencyPlan plan = plan_residency(std::vector<int64_t>((size_t)(nlocal - keep), nb), LM_GENOMES_HOST, 0, LM_RES_SEGMENT_BYTES);
-                plan.place.insert(plan.place.begin(), (size_t)keep, GenomePlace()); // (the kept genomes: in the device store)
-                plan.genomes_device = keep;
-                plan.bytes_device = keep * sp.gbytes;
-                if (!lm_res_alloc_host(ix, plan, g_open_error)) {
-                    delete ix;
-                    return LM_ERR_NOMEM;
-                }
-                for (int64_t l = keep; l < nlocal; l++) { // (pinned destination: DMA at the link's rate, one copy per genome)
-                    const GenomePlace &pl = plan.place[(size_t)l];
-                    HIPCHK(hipMemcpyAsync(ix->g_host_segs[(size_t)pl.seg].p + pl.off, ix->d_gbits.p + l * sp.gbytes, (size_t)nb,
-                                          hipMemcpyDeviceToHost, ix->st));
-                    h.genomes[(size_t)l].bits_off = -1; // (not in the device store)
-                    goff[(size_t)l] = -1;
-                }
-                bsync(ix);
-                {   // the device store shrinks to the genomes that stay (same offsets: they are the first `keep` slots)
-                    DBuf<uint8_t> kept;
-                    kept.alloc_exact((size_t)(keep * sp.gbytes) + 64, true, ix->st);
-                    if (keep > 0) HIPCHK(hipMemcpyAsync(kept.p, ix->d_gbits.p, (size_t)(keep * sp.gbytes), hipMemcpyDeviceToDevice, ix->st));
-                    bsync(ix);
-                    ix->d_gbits.release();
-                    std::swap(ix->d_gbits.p, kept.p);
-                    std::swap(ix->d_gbits.cap, kept.cap);
-                }
-                copy_up(ix->d_g_off, goff);
-                bsync(ix);
-                ix->view.gbits = ix->d_gbits.p;
-            }
-        }
-        ix->hbm_bytes = ix->seed_bytes + (int64_t)((uint64_t)ix->res.genome_bytes_device + 64 + (uint64_t)M * 8 + pfx.size() * 4 + nlocal * 20);
-        lm_set_scratch_budget(ix);
-    } catch (const std::exception &e) {
-        g_open_error = e.what();
-        delete ix;
-        return LM_ERR_HIP;
-    }
-    *out = ix;
-    return LM_OK;
-}
-
-lm_status lm_index_fetch(lm_index *ix, int64_t local_genome, int64_t start, int64_t len, uint8_t *out) {
-    if (!ix || local_genome < 0 || local_genome >= (int64_t)ix->host.genomes.size()) return LM_ERR_ARG;
-    const HostGenome &G = ix->host.genomes[local_genome];
-    if (start < 0 || len < 0 || start + len > G.len) return LM_ERR_ARG;
-    try {
-        std::lock_guard<std::mutex> lock(ix->mu);
-        HIPCHK(hipSetDevice(ix->device));
-        DBuf<uint8_t> d;
-        d.ensure((size_t)len + 1);
-        // (a host-resident genome is read where it lives: this kernel and k_stage_genome_bits are the two that may)
-        const uint8_t *gsrc = !ix->g_hptr.empty() && ix->g_hptr[(size_t)local_genome] ? ix->g_hptr[(size_t)local_genome] : ix->d_gbits.p + G.bits_off;
-        hipLaunchKernelGGL(k_fetch_bases, dim3(gridn(len)), dim3(256), 0, ix->st, gsrc, start, len, d.p);
-        HIPCHK(hipMemcpyAsync(out, d.p, (size_t)len, hipMemcpyDeviceToHost, ix->st));
-        bsync(ix);
-    } catch (const std::exception &e) {
-        ix->err = e.what();
-        return LM_ERR_HIP;
-    }
-    return LM_OK;
-}
-
-} // extern "C"
-
 // =====================================================================================================================
-// Index from caller-supplied genomes (lm_index_builder_*, include/lexicmap_hip.h).  The synthetic builder
-// above stays as it is (the benchmark's input); what follows are its siblings for genome records of any length, with
-// several contigs and skip regions: geometry from tables (g_off / g_len / g_bg + a CSR of skip regions) instead of
-// SynthDev, and the one masking rule the synthetic set never needs - a mask no k-mer of the genome shares its p-base
-// prefix with captures the argmin over ALL k-mers (lexichash MaskKnownDistinctPrefixes(..., checkShorterPrefix = true),
-// lib-index-build.go:1028).  Planner (records, spacers, skip regions, keys, shards): lm_build_plan.h.
-#include "lm_build_plan.h"
-
-namespace lm {
-
+// The seed kernels.  Geometry comes from tables, so that one set of kernels serves records of any length: g_off / g_len /
+// g_bg per record and a CSR of skip regions (spacers between contigs, runs of N; empty for a synthetic set).
 struct GenomeTab {
     const int64_t *g_off;   // [nlocal] byte offset of the record in the store
     const int32_t *g_len;   // [nlocal] bases
@@ -922,12 +311,17 @@ __global__ void k_pack_record(const uint8_t *__restrict__ ascii, const int64_t *
     }
 }
 
-// k_capture_lds for records described by tables.  LDS = true: the per-mask minima in LDS as above; false (more masks than a
-// CU's LDS holds): in ghash[block][M].  Phase 1: argmin over the k-mers sharing a mask's prefix, k-mers that overlap a skip
-// region left out.  Phase 1b, the missing-prefix rule: a mask whose minimum is still untouched takes the argmin over ALL
+// LexicHash capture of one record by one workgroup, all phases in one launch.  LDS = true: the per-mask minima live in LDS
+// (M x 8 B = 160 KB for the default 20000 masks: the whole LDS of a CU) instead of a global table hammered with atomics;
+// false (more masks than a CU's LDS holds): in ghash[block][M].  Masks of a p-base prefix are found without a table in
+// memory: in a lexicmap mask set every prefix has one mask and some have two (docs/content/usage/utils/masks.md:69-110),
+// so first(pf) = pf + #doubled prefixes below pf: a 4^p-bit map + per-word counts (2.5 KB).
+// Phase 1: ds_min_u64 of mask^kmer over the k-mers sharing a mask's prefix, k-mers that overlap a skip region left out.
+// Phase 1b, the missing-prefix rule: a mask whose minimum is still untouched takes the argmin over ALL
 // k-mers of both strands - one lane per such mask, the k-mers cut 64 at a time and passed round the wavefront; the lane also
 // counts the occurrences of its minimum and keeps the first.  A wavefront without such a mask skips the sweep, so a genome
-// in which every prefix occurs (5 Mb: 600 k-mers per prefix) pays one pass over the minima.  Phase 2 as above, plus the
+// in which every prefix occurs (5 Mb: 600 k-mers per prefix) pays one pass over the minima.  Phase 2: every k-mer equal to
+// its mask's minimum is emitted (all occurrences, lib-index-build.go:1028-1046), low-complexity captures dropped, plus the
 // captures of phase 1b from what their lanes kept (a k-mer that occurs more than once is looked up again).
 // miss_pos / miss_cnt: [block][M] scratch, (pos << 1 | strand) + 1 of the first occurrence (0: captured in phase 1 or not at
 // all) and the number of occurrences.
@@ -1039,7 +433,8 @@ __global__ __launch_bounds__(1024) void k_capture_g(GenomeTab gt, MaskTab mt, co
     __syncthreads();
     if (stamp) clk[2] = wall_clock64();
     const uint64_t bg = gt.g_bg[l];
-    // ---- phase 2: count, reserve one range of the staging arrays for the record, write (k_capture_lds)
+    // ---- phase 2: count, reserve ONE contiguous range of the staging arrays for the record (a per-capture atomic on the
+    // shared counter costs more than the whole sweep), write
     uint32_t *wsum = bc + nw; // [16] wave totals
     __shared__ unsigned long long base_seed, base_pos;
     uint32_t mine = 0;
@@ -1141,10 +536,16 @@ __global__ void k_pseudo_pos_g(GenomeTab gt, int64_t l0, int nchunk, int K, uint
     if (c < nchunk) pos_keys[base + c] = ((uint64_t)c << 32) | ((uint64_t)(uint32_t)(gt.g_len[l0 + c] - K) << 1) | 1ull; // sorts last
 }
 
-// k_desert_fill for records described by tables: the walk starts from pre = 0 and ends at the pseudo position len - K of THAT
-// record, the window is clipped to that record, and a candidate whose k-mer overlaps a skip region is passed over in the
-// upstream and in the downstream scan (add_one's in_intervals) - the window masking itself ignores skip regions
-// (MaskKnownDistinctPrefixes(window, nil, false), lib-index-build.go:1198).
+// Desert filling, lib-index-build.go:1094-1407, as the reference does it: for every pair of neighbouring seeds at least
+// max_desert apart, walk from pre + seed_dist in steps of seed_dist; at each step scan seed_pos_r positions upstream, then
+// downstream, for a non-low-complexity k-mer (+ strand before - strand) that IS THE CAPTURE OF SOME MASK WHEN THE WINDOW
+// [pre - 1000, pos + 1000 + k) ALONE IS MASKED (MaskKnownDistinctPrefixes(window, nil, false), :1191-1240), and store it
+// under that mask - the LAST (largest-index) mask that captures it.  A wavefront takes 64 seed pairs, finds the deserts
+// among them and walks them one after the other; the capture test of a candidate is a sweep of the window by the 64 lanes
+// (is any window k-mer of either strand with the same p-base prefix closer to the mask?).  The walk starts from pre = 0
+// and ends at the pseudo position len - K of THAT record, the window is clipped to that record, and a candidate whose
+// k-mer overlaps a skip region is passed over in the upstream and in the downstream scan (add_one's in_intervals) - the
+// window masking itself ignores skip regions (MaskKnownDistinctPrefixes(window, nil, false), lib-index-build.go:1198).
 __global__ __launch_bounds__(256) void k_desert_fill_g(GenomeTab gt, MaskTab mt, const uint8_t *__restrict__ gbits, int64_t l0,
                                                         const uint64_t *__restrict__ pos_keys, int64_t npk, int max_desert,
                                                         int seed_dist, uint16_t *__restrict__ s_mask,
@@ -1260,12 +661,10 @@ struct lm_index_builder {
     };
     std::vector<std::unique_ptr<Slab>> slabs;
     int64_t slab_bytes = (int64_t)256 << 20, store_bytes = 0;
-    int64_t stage_seeds = 0;          // > 0 (LM_BUILD_STAGE_SEEDS): first size of the seed staging arrays instead of the estimate
     // lm_index_builder_extend: the index this builder continues (borrowed, only read), how many of ix->host.genomes are its
     // local records (they lie in front, their store slots planned but not filled before finish) and its record count over all shards
     lm_index *base = nullptr;
     int64_t nbase = 0, base_records = 0;
-    int64_t piece_seeds = 0;          // > 0 (LM_BUILD_STAGE_SEEDS): the base's seeds are decoded in pieces of at most this many
     std::vector<int32_t> reg_off{0}, reg_s, reg_e; // skip regions of the local records (CSR)
     std::vector<int32_t> g2local;                  // sharded: record number -> local number or -1
     std::vector<int32_t> pfx;
@@ -1329,18 +728,413 @@ static int64_t builder_pack(lm_index_builder *b, const BuildRecord &r, const lm_
     return off;
 }
 
-static void builder_finish(lm_index_builder *b, const lm_res_request &rq) {
-    lm_index *ix = b->ix;
+// the host refused the pinned memory for the records beyond the residency budget: LM_ERR_NOMEM in every front end
+struct PinnedOOM : DeviceOOM {
+    using DeviceOOM::DeviceOOM;
+};
+
+// The settings of the seed pipeline, checked once for all front ends; false: `err` says what is wrong (LM_ERR_ARG).
+// gen_masks puts every p-base prefix once and the rest on distinct prefixes, so it makes at most 2 * 4^p masks; a desert
+// walk advances by seed_dist.
+static bool seed_settings_ok(const char *who, int k, int masks, int max_desert, int seed_dist, std::string &err) {
+    if (k != 31 || masks < 4 || masks > 65535 || max_desert < 1 || seed_dist < 1) {
+        err = std::string(who) + ": unsupported settings (k must be 31, masks in [4, 65535], max_desert and seed_dist >= 1)";
+        return false;
+    }
+    const int p = mask_prefix_of(masks);
+    if (masks > 2 * (1 << (2 * p))) {
+        err = std::string(who) + ": " + std::to_string(masks) + " masks need more than two masks per " + std::to_string(p) +
+              "-base prefix, which the mask generator of this build does not make (at most " + std::to_string(2 * (1 << (2 * p))) + ")";
+        return false;
+    }
+    return true;
+}
+static bool build_opt_ok(const char *who, const lm_build_opt &bo, std::string &err) {
+    if (!seed_settings_ok(who, bo.k, bo.masks, bo.max_desert, bo.seed_dist, err)) return false;
+    if (bo.genome_batch_size < 1 || bo.genome_batch_size > (1 << 17) || bo.contig_interval < 0 || bo.contig_interval >= (1 << 28) ||
+        bo.max_genome >= (1 << 28)) {
+        err = std::string(who) + ": unsupported build options (genome_batch_size in [1, 2^17], contig_interval >= 0, max_genome < 2^28)";
+        return false;
+    }
+    return true;
+}
+
+// What every front end begins with, ix->opt and ix->device being set: the stream, the HostIndex header, the mask set
+// (generated, or the masks of the index `bh` that is continued), pfx[f] = first mask of the p-base prefix f - every prefix
+// once or twice, which is what lets k_capture_g find the masks of a prefix without a table - and the upload of both.
+// LM_OK, or the status to return with its text in g_open_error.
+static lm_status builder_header(lm_index *ix, int K, int M, int64_t mask_seed, int contig_interval, const HostIndex *bh, std::vector<int32_t> &pfx) {
+    HIPCHK(hipSetDevice(ix->device));
+    HIPCHK(hipStreamCreate(&ix->st));
+    const lm_options &opt = ix->opt;
     HostIndex &h = ix->host;
-    const lm_build_opt &bo = b->bo;
+    const int p = bh ? bh->mask_prefix : mask_prefix_of(M);
+    h.k = K;
+    h.M = M;
+    h.main_version = 3;
+    h.minor_version = 5;
+    h.synthetic = false;
+    h.mask_prefix = p;
+    h.anchor_prefix = bh ? bh->anchor_prefix : 6;
+    h.contig_interval = contig_interval;
+    h.shard_rank = bh ? bh->shard_rank : opt.shard_count > 1 ? opt.shard_rank : 0;
+    h.shard_count = bh ? bh->shard_count : opt.shard_count > 1 ? opt.shard_count : 1;
+    if (h.shard_rank < 0 || h.shard_rank >= h.shard_count) {
+        g_open_error = "index build: shard_rank outside [0, shard_count)";
+        return LM_ERR_OPTION;
+    }
+    if (!bh && (opt.min_prefix > K || opt.min_prefix < p + h.anchor_prefix)) { // (a base's options passed when it was made)
+        g_open_error = "MinPrefix out of range for this index";
+        return LM_ERR_OPTION;
+    }
+    if (bh) h.masks = bh->masks;
+    else gen_masks(K, M, (uint64_t)mask_seed, h.masks);
+    pfx.assign((size_t)(1ull << (2 * p)) + 1, 0);
+    for (int i = 0; i < M; i++) pfx[(size_t)(h.masks[(size_t)i] >> ((K - p) << 1)) + 1]++;
+    for (size_t i = 1; i < pfx.size(); i++) {
+        if (pfx[i] < 1 || pfx[i] > 2) {
+            g_open_error = "index build: the mask set does not have every " + std::to_string(p) + "-base prefix once or twice";
+            return LM_ERR_ARG;
+        }
+        pfx[i] += pfx[i - 1];
+    }
+    ix->d_masks.ensure((size_t)M);
+    ix->d_pfx_first.ensure(pfx.size());
+    HIPCHK(hipMemcpyAsync(ix->d_masks.p, h.masks.data(), (size_t)M * 8, hipMemcpyHostToDevice, ix->st));
+    HIPCHK(hipMemcpyAsync(ix->d_pfx_first.p, pfx.data(), pfx.size() * 4, hipMemcpyHostToDevice, ix->st));
+    bsync(ix);
+    return LM_OK;
+}
+
+// The seed pipeline, what every front end ends in.  In: the header and `pfx` of builder_header; the 2-bit store ix->d_gbits
+// with the records in slots of build_slot_bytes back to back, described by h.genomes (bits_off, len, bg); h.batch_first;
+// h.g2local where the records of a sharded set are numbered through a table.  It uploads the tables, fills in the view,
+// generates the seeds and applies the residency request `rq`.
+// Seeds are generated per chunk of records into staging arrays and shown to the packer, twice (count, place): the unpacked
+// seeds of the whole set never exist (they would not fit beside the packed image at BASELINE configs 3-5).  A chunk holds
+// at most chunk_records records and chunk_bases bases - the caller's choice: a record of a chunk costs 16 B x masks of
+// scratch (24 B with the minima in a global table), a chunk one host synchronisation per phase.
+// reg_off / reg_s / reg_e: CSR of the skip regions of every record (all zeros: none).  base, nbase: the records [0, nbase)
+// are those of the resident index `base`; their seeds are decoded from its image, not captured again.
+static void build_seed_index(lm_index *ix, const std::vector<int32_t> &pfx, const std::vector<int32_t> &reg_off, const std::vector<int32_t> &reg_s,
+                             const std::vector<int32_t> &reg_e, int max_desert, int seed_dist, int64_t chunk_records, int64_t chunk_bases,
+                             const lm_index *base, int64_t nbase, const lm_res_request &rq) {
+    HostIndex &h = ix->host;
     const int K = h.k, M = h.M, p = h.mask_prefix;
     const int64_t nlocal = (int64_t)h.genomes.size();
     const bool dbg = getenv("LM_DEBUG") != nullptr;
     const double t0 = now_ms();
+    // measurement / tests only, results do not depend on it: a first size of the staging arrays that
+    // overflows, and (the base's seeds may be decoded in pieces smaller than what a capture needs) the largest decode piece
+    int64_t stage_seeds = 0, piece_seeds = 0;
+    if (const char *e = getenv("LM_BUILD_STAGE_SEEDS")) {
+        stage_seeds = std::max<int64_t>(1024, atoll(e));
+        piece_seeds = std::max<int64_t>(4, atoll(e));
+    }
     auto copy_up = [&](auto &dbuf, const auto &vec) {
         dbuf.ensure(std::max<size_t>(vec.size(), 1));
         if (!vec.empty()) HIPCHK(hipMemcpyAsync(dbuf.p, vec.data(), vec.size() * sizeof(vec[0]), hipMemcpyHostToDevice, ix->st));
     };
+    // ---- tables
+    std::vector<int64_t> goff((size_t)nlocal), slot((size_t)nlocal);
+    std::vector<int32_t> glen((size_t)nlocal);
+    std::vector<uint64_t> gbg((size_t)nlocal);
+    int64_t max_len = 1;
+    for (int64_t l = 0; l < nlocal; l++) {
+        const HostGenome &G = h.genomes[(size_t)l];
+        goff[(size_t)l] = G.bits_off;
+        glen[(size_t)l] = G.len;
+        gbg[(size_t)l] = G.bg;
+        slot[(size_t)l] = build_slot_bytes(G.len);
+        max_len = std::max<int64_t>(max_len, G.len);
+        ix->bg2local[G.bg] = (int)l;
+    }
+    const int64_t store_bytes = nlocal ? goff.back() + slot.back() : 0;
+    copy_up(ix->d_g_off, goff);
+    copy_up(ix->d_g_len, glen);
+    copy_up(ix->d_g_bg, gbg);
+    copy_up(ix->d_batch_first, h.batch_first);
+    if (!h.g2local.empty()) copy_up(ix->d_g2local, h.g2local);
+    DBuf<int32_t> d_reg_off, d_reg_s, d_reg_e;
+    copy_up(d_reg_off, reg_off);
+    copy_up(d_reg_s, reg_s);
+    copy_up(d_reg_e, reg_e);
+    lm_fill_gap_lut(ix); // same table as lm_index_open (lib-chaining.go:662-667)
+    bsync(ix);
+    DevIndexView &v = ix->view;
+    v.K = K;
+    v.M = M;
+    v.mask_prefix = p;
+    v.masks = ix->d_masks.p;
+    v.pfx_first = ix->d_pfx_first.p;
+    v.g_bg = ix->d_g_bg.p;
+    v.gbits = ix->d_gbits.p;
+    v.g_off = ix->d_g_off.p;
+    v.g_len = ix->d_g_len.p;
+    v.batch_first = ix->d_batch_first.p;
+    v.nbatches = h.genome_batches;
+    v.ngenomes = nlocal;
+    v.shard_rank = h.shard_rank;
+    v.shard_count = h.shard_count;
+    v.g2local = h.g2local.empty() ? nullptr : ix->d_g2local.p;
+    const MaskTab mt{ix->d_masks.p, ix->d_pfx_first.p, K, p, M};
+    const GenomeTab gt{ix->d_g_off.p, ix->d_g_len.p, ix->d_g_bg.p, d_reg_off.p, d_reg_s.p, d_reg_e.p};
+    // ---- prefix -> masks without a table in memory (k_capture_g): every prefix once or twice (checked by builder_header)
+    const int npfx = 1 << (2 * p), nwords = (npfx + 63) >> 6;
+    std::vector<uint64_t> dmap((size_t)nwords, 0);
+    std::vector<uint32_t> dcnt((size_t)nwords, 0);
+    for (int f = 0; f < npfx; f++)
+        if (pfx[(size_t)f + 1] - pfx[(size_t)f] == 2) dmap[(size_t)(f >> 6)] |= 1ull << (f & 63);
+    for (int w = 1; w < nwords; w++) dcnt[(size_t)w] = dcnt[(size_t)w - 1] + (uint32_t)__builtin_popcountll(dmap[(size_t)w - 1]);
+    // capture in LDS when the per-mask minima fit a CU's LDS, otherwise minima in a global table
+    const size_t lds_full = (size_t)M * 8 + (size_t)nwords * 12 + 64;
+    const bool lds_capture = lds_full <= 160 * 1024;
+    const size_t lds_bytes = lds_capture ? lds_full : (size_t)nwords * 12 + 64;
+    DBuf<uint64_t> dbl_map;
+    DBuf<uint32_t> dbl_cnt;
+    copy_up(dbl_map, dmap);
+    copy_up(dbl_cnt, dcnt);
+    if (lds_capture && lds_bytes > 64 * 1024)
+        HIPCHK(hipFuncSetAttribute((const void *)k_capture_g<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    // ---- chunks of records within the caller's limits (and 192 MB of minima where they live in a global table); the staging
+    // arrays are sized from the largest chunk with one estimate per record
+    const int64_t ch_max = std::max<int64_t>(1, lds_capture ? chunk_records : std::min<int64_t>(chunk_records, ((int64_t)192 << 20) / ((int64_t)M * 8)));
+    struct Chunk {
+        int64_t l0;
+        int n;
+        double seeds, pos;
+    };
+    std::vector<Chunk> chunks; // (of the added records only)
+    for (int64_t l = nbase; l < nlocal;) {
+        Chunk c{l, 0, 0, 0};
+        int64_t bases = 0;
+        while (l < nlocal && c.n < ch_max && (c.n == 0 || bases + glen[(size_t)l] <= chunk_bases)) {
+            bases += glen[(size_t)l];
+            c.seeds += 2.0 * (1.45 * M + (double)glen[(size_t)l] / 42.0) + 1024;
+            c.pos += 1.45 * M + 64;
+            c.n++;
+            l++;
+        }
+        chunks.push_back(c);
+    }
+    int ch_n = 1;
+    double est_seeds = 0, est_pos = 0;
+    for (auto &c : chunks) {
+        ch_n = std::max(ch_n, c.n);
+        est_seeds = std::max(est_seeds, c.seeds);
+        est_pos = std::max(est_pos, c.pos);
+    }
+    unsigned long long cap = (unsigned long long)est_seeds + 65536, pos_cap = (unsigned long long)est_pos + (unsigned long long)ch_n + 64;
+    // the base's seeds pass through the same arrays in pieces: large enough that a big image is not cut into thousands of launches
+    std::vector<int64_t> base_md_off, base_out_off;
+    int64_t base_main = 0, base_out = 0;
+    if (base) {
+        base_md_off.resize((size_t)2 * M + 1);
+        base_out_off.resize((size_t)2 * M + 1);
+        HIPCHK(hipMemcpyAsync(base_md_off.data(), base->d_md_off.p, base_md_off.size() * 8, hipMemcpyDeviceToHost, ix->st));
+        HIPCHK(hipMemcpyAsync(base_out_off.data(), base->d_out_off.p, base_out_off.size() * 8, hipMemcpyDeviceToHost, ix->st));
+        bsync(ix);
+        base_main = base_md_off.back();
+        base_out = base_out_off.back();
+        cap = std::max<unsigned long long>(cap, (unsigned long long)std::min<int64_t>(std::max(base_main, base_out), (int64_t)1 << 26));
+    }
+    if (stage_seeds > 0) { // (tests: a first estimate that is too small, so that the enlarge-and-retry path runs)
+        cap = (unsigned long long)stage_seeds;
+        pos_cap = (unsigned long long)stage_seeds + (unsigned long long)ch_n + 64;
+    }
+    DBuf<uint16_t> s_mask;
+    DBuf<uint64_t> s_kmer, s_val, pos_keys, pos_keys2;
+    auto size_staging = [&]() {
+        s_mask.alloc_exact(cap);
+        s_kmer.alloc_exact(cap);
+        s_val.alloc_exact(cap);
+        pos_keys.alloc_exact(pos_cap);
+        pos_keys2.alloc_exact(pos_cap);
+    };
+    size_staging();
+    DBuf<unsigned long long> counters, hashes;
+    counters.ensure(8);
+    hashes.alloc_exact(lds_capture ? 1 : (size_t)ch_n * M);
+    DBuf<uint32_t> miss_pos, miss_cnt;
+    miss_pos.alloc_exact((size_t)ch_n * M);
+    miss_cnt.alloc_exact((size_t)ch_n * M);
+    SeedPacker packer;
+    packer.begin(ix, nlocal, max_len);
+    double t_cap = 0, t_desert = 0, t_pack = 0;
+    // the seeds of one chunk in the staging arrays; false: an array was too small - `cap` / `pos_cap` are what it takes
+    // (nothing was written past an array: every store is guarded by its capacity)
+    auto generate = [&](const Chunk &c, unsigned long long &nseeds) {
+        const unsigned long long pos_lim = pos_cap - (unsigned long long)c.n - 1;
+        const double ta = now_ms();
+        HIPCHK(hipMemsetAsync(counters.p, 0, 2 * sizeof(unsigned long long), ix->st));
+        if (lds_capture)
+            hipLaunchKernelGGL(k_capture_g<true>, dim3(c.n), dim3(1024), lds_bytes, ix->st, gt, mt, ix->d_gbits.p, c.l0, dbl_map.p, dbl_cnt.p,
+                               hashes.p, miss_pos.p, miss_cnt.p, s_mask.p, s_kmer.p, s_val.p, counters.p, cap, pos_keys.p, counters.p + 1, pos_lim, dbg ? counters.p + 4 : nullptr);
+        else
+            hipLaunchKernelGGL(k_capture_g<false>, dim3(c.n), dim3(1024), lds_bytes, ix->st, gt, mt, ix->d_gbits.p, c.l0, dbl_map.p, dbl_cnt.p,
+                               hashes.p, miss_pos.p, miss_cnt.p, s_mask.p, s_kmer.p, s_val.p, counters.p, cap, pos_keys.p, counters.p + 1, pos_lim, dbg ? counters.p + 4 : nullptr);
+        HIPCHK(hipGetLastError());
+        unsigned long long hc[8];
+        HIPCHK(hipMemcpyAsync(hc, counters.p, sizeof hc, hipMemcpyDeviceToHost, ix->st));
+        bsync(ix);
+        const double tb = now_ms();
+        t_cap += tb - ta;
+        if (dbg)
+            fprintf(stderr, "[lm] builder: capture of record %lld (%d bases): argmin %.3f ms, missing-prefix pass %.3f ms, emit %.3f ms\n",
+                    (long long)c.l0, glen[(size_t)c.l0], (double)(hc[5] - hc[4]) * 1e-5, (double)(hc[6] - hc[5]) * 1e-5, (double)(hc[7] - hc[6]) * 1e-5);
+        if (hc[0] >= cap || hc[1] >= pos_lim) {
+            // (desert and reversed seeds come on top of the captures: about as many again, twice over)
+            cap = std::max(cap, hc[0] * 4 + 65536);
+            pos_cap = std::max(pos_cap, hc[1] * 2 + (unsigned long long)ch_n + 64);
+            return false;
+        }
+        unsigned long long npk = hc[1];
+        hipLaunchKernelGGL(k_pseudo_pos_g, dim3((c.n + 63) / 64), dim3(64), 0, ix->st, gt, c.l0, c.n, K, pos_keys.p, npk);
+        npk += (unsigned long long)c.n;
+        prim_sort_keys(ix->st, ix->tmp, pos_keys.p, pos_keys2.p, (size_t)npk, 0, 64);
+        hipLaunchKernelGGL(k_desert_fill_g, dim3(gridn(((int64_t)npk + 63) / 64, 4)), dim3(256), 0, ix->st, gt, mt, ix->d_gbits.p, c.l0,
+                           pos_keys2.p, (int64_t)npk, max_desert, seed_dist, s_mask.p, s_kmer.p, s_val.p, counters.p, cap);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(hc, counters.p, sizeof hc, hipMemcpyDeviceToHost, ix->st));
+        bsync(ix);
+        if (hc[0] >= cap) {
+            cap = hc[0] * 3 + 65536;
+            return false;
+        }
+        const unsigned long long upto = hc[0];
+        hipLaunchKernelGGL(k_reverse_seeds, dim3(gridn((int64_t)upto)), dim3(256), 0, ix->st, mt, 0ull, upto, s_mask.p, s_kmer.p, s_val.p,
+                           counters.p, cap);
+        HIPCHK(hipMemcpyAsync(hc, counters.p, sizeof hc, hipMemcpyDeviceToHost, ix->st));
+        bsync(ix);
+        if (hc[0] >= cap) {
+            cap = hc[0] + hc[0] / 4 + 65536;
+            return false;
+        }
+        nseeds = hc[0];
+        t_desert += now_ms() - tb;
+        return true;
+    };
+    double t_base = 0, t_dump = 0;
+    for (int pass = 0; pass < 2; pass++) {
+        if (base) {
+            // the base's seeds first, decoded in pieces no larger than the staging arrays (a list longer than a piece is cut);
+            // every value is re-encoded by the packer: gid_bits / pos_bits of the extended set may be wider than the base's
+            const double tb0 = now_ms();
+            const int64_t piece = piece_seeds > 0 ? std::min<int64_t>(piece_seeds, (int64_t)cap) : (int64_t)cap;
+            for (int flat = 0; flat < 2; flat++) {
+                const int64_t total = flat ? base_out : base_main;
+                for (int64_t s0 = 0; s0 < total; s0 += piece) {
+                    const int64_t n = std::min<int64_t>(piece, total - s0);
+                    const double td0 = dbg ? (bsync(ix), now_ms()) : 0;
+                    sp_dump_range(base, ix->st, flat ? base_out_off : base_md_off, flat != 0, s0, s0 + n, s_mask.p, s_kmer.p, s_val.p);
+                    if (dbg) {
+                        bsync(ix);
+                        t_dump += now_ms() - td0;
+                    }
+                    if (pass == 0) packer.count(s_mask.p, s_kmer.p, s_val.p, n);
+                    else packer.place(s_mask.p, s_kmer.p, s_val.p, n);
+                }
+            }
+            bsync(ix);
+            t_base += now_ms() - tb0;
+            if (dbg)
+                fprintf(stderr, "[lm] builder pass %d: the base's %lld seeds (%lld outliers) decoded and packed in pieces of %lld: %.1f ms, "
+                                "of which the decode kernel %.1f ms (cumulative)\n", pass, (long long)(base_main + base_out), (long long)base_out,
+                        (long long)piece, t_base, t_dump);
+        }
+        for (const Chunk &c : chunks) {
+            unsigned long long n = 0;
+            for (int attempt = 0; !generate(c, n); attempt++) {
+                // a record set that outgrows the estimate (a k-mer repeated thousands of times under many masks) takes a larger try
+                if (attempt >= 4) throw HipError("index build: the seed staging buffers outgrew four enlargements");
+                if (dbg) fprintf(stderr, "[lm] builder: staging buffers enlarged to %llu seeds / %llu positions\n", cap, pos_cap);
+                size_staging();
+            }
+            const double tc = now_ms();
+            if (pass == 0) packer.count(s_mask.p, s_kmer.p, s_val.p, (int64_t)n);
+            else packer.place(s_mask.p, s_kmer.p, s_val.p, (int64_t)n);
+            bsync(ix);
+            t_pack += now_ms() - tc;
+        }
+        if (pass == 0) packer.end_count();
+        if (dbg)
+            fprintf(stderr, "[lm] builder pass %d: capture %.1f ms, desert+reverse %.1f ms, packer %.1f ms (cumulative)\n", pass, t_cap,
+                    t_desert, t_pack);
+    }
+    hashes.release();
+    miss_pos.release();
+    miss_cnt.release();
+    pos_keys.release();
+    pos_keys2.release();
+    s_mask.release();
+    s_kmer.release();
+    s_val.release();
+    const double tf = now_ms();
+    packer.finish();
+    if (dbg)
+        fprintf(stderr, "[lm] builder: partition sort %.1f ms; %lld records, %lld seeds (%lld outliers), %.2f B/seed; seed pipeline %.1f ms\n",
+                now_ms() - tf, (long long)nlocal, (long long)ix->n_seeds, (long long)ix->n_seeds_outlier,
+                (double)ix->seed_bytes / std::max<double>(1.0, (double)ix->n_seeds), now_ms() - t0);
+    ix->tmp.release();
+    // ---- residency: the set is built in HBM as ever; the records beyond the budget then move to pinned host memory and the
+    // device store shrinks to the rest (a set that does not fit the device DURING the build is out of reach of this form)
+    ix->res.genomes_device = nlocal;
+    ix->res.genome_bytes_device = store_bytes;
+    {
+        int64_t budget = rq.budget;
+        if (rq.mode == LM_GENOMES_AUTO && budget == 0) {
+            size_t fr = 0, tot = 0;
+            HIPCHK(hipMemGetInfo(&fr, &tot));
+            budget = lm_res_auto_budget((int64_t)fr + store_bytes, 0); // (the store itself is part of what it may take)
+        }
+        // the budget is counted in the store's slots: the first `keep` records stay, the rest go to the host - the planner
+        // lays out the host side only
+        int64_t keep = rq.mode == LM_GENOMES_HOST ? 0 : nlocal;
+        if (rq.mode == LM_GENOMES_AUTO)
+            for (keep = 0; keep < nlocal && goff[(size_t)keep] + slot[(size_t)keep] <= budget;) keep++;
+        if (keep < nlocal) {
+            const int64_t kept_bytes = keep > 0 ? goff[(size_t)keep - 1] + slot[(size_t)keep - 1] : 0;
+            std::vector<int64_t> nbs;
+            for (int64_t l = keep; l < nlocal; l++) nbs.push_back(((int64_t)glen[(size_t)l] + 3) >> 2);
+            ResidencyPlan plan = plan_residency(nbs, LM_GENOMES_HOST, 0, LM_RES_SEGMENT_BYTES);
+            plan.place.insert(plan.place.begin(), (size_t)keep, GenomePlace()); // (the kept records: in the device store)
+            plan.genomes_device = keep;
+            plan.bytes_device = kept_bytes;
+            std::string e;
+            if (!lm_res_alloc_host(ix, plan, e)) throw PinnedOOM(e);
+            for (int64_t l = keep; l < nlocal; l++) { // (pinned destination: DMA at the link's rate, one copy per record)
+                const GenomePlace &pl = plan.place[(size_t)l];
+                HIPCHK(hipMemcpyAsync(ix->g_host_segs[(size_t)pl.seg].p + pl.off, ix->d_gbits.p + goff[(size_t)l], (size_t)nbs[(size_t)(l - keep)],
+                                      hipMemcpyDeviceToHost, ix->st));
+                h.genomes[(size_t)l].bits_off = -1; // (not in the device store)
+                goff[(size_t)l] = -1;
+            }
+            bsync(ix);
+            {   // the device store shrinks to the records that stay (same offsets: they are its first bytes)
+                DBuf<uint8_t> kept;
+                kept.alloc_exact((size_t)kept_bytes + 64, true, ix->st);
+                if (kept_bytes > 0) HIPCHK(hipMemcpyAsync(kept.p, ix->d_gbits.p, (size_t)kept_bytes, hipMemcpyDeviceToDevice, ix->st));
+                bsync(ix);
+                ix->d_gbits.release();
+                std::swap(ix->d_gbits.p, kept.p);
+                std::swap(ix->d_gbits.cap, kept.cap);
+            }
+            copy_up(ix->d_g_off, goff);
+            bsync(ix);
+            ix->view.gbits = ix->d_gbits.p;
+        }
+    }
+    ix->hbm_bytes = ix->seed_bytes + (int64_t)((uint64_t)ix->res.genome_bytes_device + 64 + (uint64_t)M * 8 + pfx.size() * 4 + (uint64_t)nlocal * 20 +
+                                               h.batch_first.size() * 8);
+    lm_set_scratch_budget(ix);
+}
+
+// The genome front end's finish: the slabs (and the base's records) into one store, the host metadata lm_index_save writes,
+// then the seed pipeline
+static void builder_finish(lm_index_builder *b) {
+    lm_index *ix = b->ix;
+    HostIndex &h = ix->host;
+    const lm_build_opt &bo = b->bo;
     // ---- the store: one allocation, the slabs copied to their places (they ARE consecutive pieces of it) and released
     b->d_ascii.release();
     ix->d_gbits.alloc_exact((size_t)b->store_bytes + 64, true, ix->st);
@@ -1380,7 +1174,7 @@ static void builder_finish(lm_index_builder *b, const lm_res_request &rq) {
         flush();
         bsync(ix);
     }
-    // ---- tables
+    // ---- host metadata
     h.total_bases = ix->opt.total_bases_override > 0 ? ix->opt.total_bases_override : b->input_bases;
     h.input_genomes = b->ninput;
     h.genome_batch_size = bo.genome_batch_size;
@@ -1392,295 +1186,13 @@ static void builder_finish(lm_index_builder *b, const lm_res_request &rq) {
     h.genome_batches = (int)((b->nrecords + bo.genome_batch_size - 1) / bo.genome_batch_size);
     h.batch_first.assign((size_t)h.genome_batches + 1, 0);
     for (int i = 0; i <= h.genome_batches; i++) h.batch_first[(size_t)i] = std::min<int64_t>((int64_t)i * bo.genome_batch_size, b->nrecords);
-    h.n_local_genomes = nlocal;
+    h.n_local_genomes = (int64_t)h.genomes.size();
     h.max_genome_len = b->max_len;
     h.has_chunks = !h.chunk_of.empty();
     if (h.shard_count > 1) h.g2local = b->g2local;
-    std::vector<int64_t> goff((size_t)nlocal), slot((size_t)nlocal);
-    std::vector<int32_t> glen((size_t)nlocal);
-    std::vector<uint64_t> gbg((size_t)nlocal);
-    for (int64_t l = 0; l < nlocal; l++) {
-        const HostGenome &G = h.genomes[(size_t)l];
-        goff[(size_t)l] = G.bits_off;
-        glen[(size_t)l] = G.len;
-        gbg[(size_t)l] = G.bg;
-        slot[(size_t)l] = build_slot_bytes(G.len);
-        ix->bg2local[G.bg] = (int)l;
-    }
-    copy_up(ix->d_g_off, goff);
-    copy_up(ix->d_g_len, glen);
-    copy_up(ix->d_g_bg, gbg);
-    copy_up(ix->d_batch_first, h.batch_first);
-    if (!h.g2local.empty()) copy_up(ix->d_g2local, h.g2local);
-    DBuf<int32_t> d_reg_off, d_reg_s, d_reg_e;
-    copy_up(d_reg_off, b->reg_off);
-    copy_up(d_reg_s, b->reg_s);
-    copy_up(d_reg_e, b->reg_e);
-    lm_fill_gap_lut(ix);
-    bsync(ix);
-    DevIndexView &v = ix->view;
-    v.K = K;
-    v.M = M;
-    v.mask_prefix = p;
-    v.masks = ix->d_masks.p;
-    v.pfx_first = ix->d_pfx_first.p;
-    v.g_bg = ix->d_g_bg.p;
-    v.gbits = ix->d_gbits.p;
-    v.g_off = ix->d_g_off.p;
-    v.g_len = ix->d_g_len.p;
-    v.batch_first = ix->d_batch_first.p;
-    v.nbatches = h.genome_batches;
-    v.ngenomes = nlocal;
-    v.shard_rank = h.shard_rank;
-    v.shard_count = h.shard_count;
-    v.g2local = h.g2local.empty() ? nullptr : ix->d_g2local.p;
-    const MaskTab mt{ix->d_masks.p, ix->d_pfx_first.p, K, p, M};
-    const GenomeTab gt{ix->d_g_off.p, ix->d_g_len.p, ix->d_g_bg.p, d_reg_off.p, d_reg_s.p, d_reg_e.p};
-    // ---- prefix -> masks without a table in memory (k_capture_lds): every prefix once or twice (checked by _new)
-    const std::vector<int32_t> &pfx = b->pfx;
-    const int npfx = 1 << (2 * p), nwords = (npfx + 63) >> 6;
-    std::vector<uint64_t> dmap((size_t)nwords, 0);
-    std::vector<uint32_t> dcnt((size_t)nwords, 0);
-    for (int f = 0; f < npfx; f++)
-        if (pfx[(size_t)f + 1] - pfx[(size_t)f] == 2) dmap[(size_t)(f >> 6)] |= 1ull << (f & 63);
-    for (int w = 1; w < nwords; w++) dcnt[(size_t)w] = dcnt[(size_t)w - 1] + (uint32_t)__builtin_popcountll(dmap[(size_t)w - 1]);
-    const size_t lds_full = (size_t)M * 8 + (size_t)nwords * 12 + 64;
-    const bool lds_capture = lds_full <= 160 * 1024;
-    const size_t lds_bytes = lds_capture ? lds_full : (size_t)nwords * 12 + 64;
-    DBuf<uint64_t> dbl_map;
-    DBuf<uint32_t> dbl_cnt;
-    copy_up(dbl_map, dmap);
-    copy_up(dbl_cnt, dcnt);
-    if (lds_capture && lds_bytes > 64 * 1024)
-        HIPCHK(hipFuncSetAttribute((const void *)k_capture_g<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    // ---- chunks of records: as many as the per-record scratch (16 B per mask) and a bound on the bases allow; the staging
-    // buffers are sized from the bases of the largest chunk with the synthetic builder's estimate per record
-    const int64_t CH_MAX = std::max<int64_t>(1, std::min<int64_t>(2048, ((int64_t)128 << 20) / ((int64_t)M * 16)));
-    const int64_t CH_BASES = (int64_t)1 << 30;
-    struct Chunk {
-        int64_t l0;
-        int n;
-        double seeds, pos;
-    };
-    std::vector<Chunk> chunks; // (of the added records only: the base's seeds are decoded from its image, not captured again)
-    for (int64_t l = nbase; l < nlocal;) {
-        Chunk c{l, 0, 0, 0};
-        int64_t bases = 0;
-        while (l < nlocal && c.n < CH_MAX && (c.n == 0 || bases + glen[(size_t)l] <= CH_BASES)) {
-            bases += glen[(size_t)l];
-            c.seeds += 2.0 * (1.45 * M + (double)glen[(size_t)l] / 42.0) + 1024;
-            c.pos += 1.45 * M + 64;
-            c.n++;
-            l++;
-        }
-        chunks.push_back(c);
-    }
-    int ch_n = 1;
-    double est_seeds = 0, est_pos = 0;
-    for (auto &c : chunks) {
-        ch_n = std::max(ch_n, c.n);
-        est_seeds = std::max(est_seeds, c.seeds);
-        est_pos = std::max(est_pos, c.pos);
-    }
-    unsigned long long cap = (unsigned long long)est_seeds + 65536, pos_cap = (unsigned long long)est_pos + (unsigned long long)ch_n + 64;
-    // the base's seeds pass through the same arrays in pieces: large enough that a big image is not cut into thousands of launches
-    std::vector<int64_t> base_md_off, base_out_off;
-    int64_t base_main = 0, base_out = 0;
-    if (base) {
-        base_md_off.resize((size_t)2 * M + 1);
-        base_out_off.resize((size_t)2 * M + 1);
-        HIPCHK(hipMemcpyAsync(base_md_off.data(), base->d_md_off.p, base_md_off.size() * 8, hipMemcpyDeviceToHost, ix->st));
-        HIPCHK(hipMemcpyAsync(base_out_off.data(), base->d_out_off.p, base_out_off.size() * 8, hipMemcpyDeviceToHost, ix->st));
-        bsync(ix);
-        base_main = base_md_off.back();
-        base_out = base_out_off.back();
-        cap = std::max<unsigned long long>(cap, (unsigned long long)std::min<int64_t>(std::max(base_main, base_out), (int64_t)1 << 26));
-    }
-    if (b->stage_seeds > 0) { // (tests: a first estimate that is too small, so that the enlarge-and-retry path runs)
-        cap = (unsigned long long)b->stage_seeds;
-        pos_cap = (unsigned long long)b->stage_seeds + (unsigned long long)ch_n + 64;
-    }
-    DBuf<uint16_t> s_mask;
-    DBuf<uint64_t> s_kmer, s_val, pos_keys, pos_keys2;
-    auto size_staging = [&]() {
-        s_mask.alloc_exact(cap);
-        s_kmer.alloc_exact(cap);
-        s_val.alloc_exact(cap);
-        pos_keys.alloc_exact(pos_cap);
-        pos_keys2.alloc_exact(pos_cap);
-    };
-    size_staging();
-    DBuf<unsigned long long> counters, hashes;
-    counters.ensure(8);
-    hashes.alloc_exact(lds_capture ? 1 : (size_t)ch_n * M);
-    DBuf<uint32_t> miss_pos, miss_cnt;
-    miss_pos.alloc_exact((size_t)ch_n * M);
-    miss_cnt.alloc_exact((size_t)ch_n * M);
-    SeedPacker packer;
-    packer.begin(ix, nlocal, b->max_len);
-    double t_cap = 0, t_desert = 0, t_pack = 0;
-    // the seeds of one chunk in the staging arrays; false: an array was too small - `cap` / `pos_cap` are what it takes
-    // (nothing was written past an array: every store is guarded by its capacity)
-    auto generate = [&](const Chunk &c, unsigned long long &nseeds) {
-        const unsigned long long pos_lim = pos_cap - (unsigned long long)c.n - 1;
-        const double ta = now_ms();
-        HIPCHK(hipMemsetAsync(counters.p, 0, 2 * sizeof(unsigned long long), ix->st));
-        if (lds_capture)
-            hipLaunchKernelGGL(k_capture_g<true>, dim3(c.n), dim3(1024), lds_bytes, ix->st, gt, mt, ix->d_gbits.p, c.l0, dbl_map.p, dbl_cnt.p,
-                               hashes.p, miss_pos.p, miss_cnt.p, s_mask.p, s_kmer.p, s_val.p, counters.p, cap, pos_keys.p, counters.p + 1, pos_lim, dbg ? counters.p + 4 : nullptr);
-        else
-            hipLaunchKernelGGL(k_capture_g<false>, dim3(c.n), dim3(1024), lds_bytes, ix->st, gt, mt, ix->d_gbits.p, c.l0, dbl_map.p, dbl_cnt.p,
-                               hashes.p, miss_pos.p, miss_cnt.p, s_mask.p, s_kmer.p, s_val.p, counters.p, cap, pos_keys.p, counters.p + 1, pos_lim, dbg ? counters.p + 4 : nullptr);
-        HIPCHK(hipGetLastError());
-        unsigned long long hc[8];
-        HIPCHK(hipMemcpyAsync(hc, counters.p, sizeof hc, hipMemcpyDeviceToHost, ix->st));
-        bsync(ix);
-        const double tb = now_ms();
-        t_cap += tb - ta;
-        if (dbg)
-            fprintf(stderr, "[lm] genome builder: capture of record %lld (%d bases): argmin %.3f ms, missing-prefix pass %.3f ms, emit %.3f ms\n",
-                    (long long)c.l0, glen[(size_t)c.l0], (double)(hc[5] - hc[4]) * 1e-5, (double)(hc[6] - hc[5]) * 1e-5, (double)(hc[7] - hc[6]) * 1e-5);
-        if (hc[0] >= cap || hc[1] >= pos_lim) {
-            // (desert and reversed seeds come on top of the captures: about as many again, twice over)
-            cap = std::max(cap, hc[0] * 4 + 65536);
-            pos_cap = std::max(pos_cap, hc[1] * 2 + (unsigned long long)ch_n + 64);
-            return false;
-        }
-        unsigned long long npk = hc[1];
-        hipLaunchKernelGGL(k_pseudo_pos_g, dim3((c.n + 63) / 64), dim3(64), 0, ix->st, gt, c.l0, c.n, K, pos_keys.p, npk);
-        npk += (unsigned long long)c.n;
-        prim_sort_keys(ix->st, ix->tmp, pos_keys.p, pos_keys2.p, (size_t)npk, 0, 64);
-        hipLaunchKernelGGL(k_desert_fill_g, dim3(gridn(((int64_t)npk + 63) / 64, 4)), dim3(256), 0, ix->st, gt, mt, ix->d_gbits.p, c.l0,
-                           pos_keys2.p, (int64_t)npk, bo.max_desert, bo.seed_dist, s_mask.p, s_kmer.p, s_val.p, counters.p, cap);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(hc, counters.p, sizeof hc, hipMemcpyDeviceToHost, ix->st));
-        bsync(ix);
-        if (hc[0] >= cap) {
-            cap = hc[0] * 3 + 65536;
-            return false;
-        }
-        const unsigned long long upto = hc[0];
-        hipLaunchKernelGGL(k_reverse_seeds, dim3(gridn((int64_t)upto)), dim3(256), 0, ix->st, mt, 0ull, upto, s_mask.p, s_kmer.p, s_val.p,
-                           counters.p, cap);
-        HIPCHK(hipMemcpyAsync(hc, counters.p, sizeof hc, hipMemcpyDeviceToHost, ix->st));
-        bsync(ix);
-        if (hc[0] >= cap) {
-            cap = hc[0] + hc[0] / 4 + 65536;
-            return false;
-        }
-        nseeds = hc[0];
-        t_desert += now_ms() - tb;
-        return true;
-    };
-    double t_base = 0, t_dump = 0;
-    for (int pass = 0; pass < 2; pass++) {
-        if (base) {
-            // the base's seeds first, decoded in pieces no larger than the staging arrays (a list longer than a piece is cut);
-            // every value is re-encoded by the packer: gid_bits / pos_bits of the extended set may be wider than the base's
-            const double tb0 = now_ms();
-            const int64_t piece = b->piece_seeds > 0 ? std::min<int64_t>(b->piece_seeds, (int64_t)cap) : (int64_t)cap;
-            for (int flat = 0; flat < 2; flat++) {
-                const int64_t total = flat ? base_out : base_main;
-                for (int64_t s0 = 0; s0 < total; s0 += piece) {
-                    const int64_t n = std::min<int64_t>(piece, total - s0);
-                    const double td0 = dbg ? (bsync(ix), now_ms()) : 0;
-                    sp_dump_range(base, ix->st, flat ? base_out_off : base_md_off, flat != 0, s0, s0 + n, s_mask.p, s_kmer.p, s_val.p);
-                    if (dbg) {
-                        bsync(ix);
-                        t_dump += now_ms() - td0;
-                    }
-                    if (pass == 0) packer.count(s_mask.p, s_kmer.p, s_val.p, n);
-                    else packer.place(s_mask.p, s_kmer.p, s_val.p, n);
-                }
-            }
-            bsync(ix);
-            t_base += now_ms() - tb0;
-            if (dbg)
-                fprintf(stderr, "[lm] genome builder pass %d: the base's %lld seeds (%lld outliers) decoded and packed in pieces of %lld: %.1f ms, "
-                                "of which the decode kernel %.1f ms (cumulative)\n", pass, (long long)(base_main + base_out), (long long)base_out,
-                        (long long)piece, t_base, t_dump);
-        }
-        for (const Chunk &c : chunks) {
-            unsigned long long n = 0;
-            for (int attempt = 0; !generate(c, n); attempt++) {
-                // a record set that outgrows the estimate (a k-mer repeated thousands of times under many masks) takes a larger try
-                if (attempt >= 4) throw HipError("genome builder: the seed staging buffers outgrew four enlargements");
-                if (dbg) fprintf(stderr, "[lm] genome builder: staging buffers enlarged to %llu seeds / %llu positions\n", cap, pos_cap);
-                size_staging();
-            }
-            const double tc = now_ms();
-            if (pass == 0) packer.count(s_mask.p, s_kmer.p, s_val.p, (int64_t)n);
-            else packer.place(s_mask.p, s_kmer.p, s_val.p, (int64_t)n);
-            bsync(ix);
-            t_pack += now_ms() - tc;
-        }
-        if (pass == 0) packer.end_count();
-        if (dbg)
-            fprintf(stderr, "[lm] genome builder pass %d: capture %.1f ms, desert+reverse %.1f ms, packer %.1f ms (cumulative)\n", pass, t_cap,
-                    t_desert, t_pack);
-    }
-    hashes.release();
-    miss_pos.release();
-    miss_cnt.release();
-    pos_keys.release();
-    pos_keys2.release();
-    s_mask.release();
-    s_kmer.release();
-    s_val.release();
-    const double tf = now_ms();
-    packer.finish();
-    if (dbg)
-        fprintf(stderr, "[lm] genome builder: partition sort %.1f ms; %lld records, %lld seeds (%lld outliers); finish %.1f ms\n", now_ms() - tf,
-                (long long)nlocal, (long long)ix->n_seeds, (long long)ix->n_seeds_outlier, now_ms() - t0);
-    ix->tmp.release();
-    // ---- residency, as lm_index_build_synthetic_ex: built in HBM, then the records beyond the budget move to pinned host memory
-    ix->res.genomes_device = nlocal;
-    ix->res.genome_bytes_device = b->store_bytes;
-    {
-        int64_t budget = rq.budget;
-        if (rq.mode == LM_GENOMES_AUTO && budget == 0) {
-            size_t fr = 0, tot = 0;
-            HIPCHK(hipMemGetInfo(&fr, &tot));
-            budget = lm_res_auto_budget((int64_t)fr + b->store_bytes, 0);
-        }
-        int64_t keep = rq.mode == LM_GENOMES_HOST ? 0 : nlocal;
-        if (rq.mode == LM_GENOMES_AUTO)
-            for (keep = 0; keep < nlocal && goff[(size_t)keep] + slot[(size_t)keep] <= budget;) keep++;
-        if (keep < nlocal) {
-            const int64_t kept_bytes = keep > 0 ? goff[(size_t)keep - 1] + slot[(size_t)keep - 1] : 0;
-            std::vector<int64_t> nbs;
-            for (int64_t l = keep; l < nlocal; l++) nbs.push_back(((int64_t)glen[(size_t)l] + 3) >> 2);
-            ResidencyPlan plan = plan_residency(nbs, LM_GENOMES_HOST, 0, LM_RES_SEGMENT_BYTES);
-            plan.place.insert(plan.place.begin(), (size_t)keep, GenomePlace()); // (the kept records: in the device store)
-            plan.genomes_device = keep;
-            plan.bytes_device = kept_bytes;
-            std::string e;
-            if (!lm_res_alloc_host(ix, plan, e)) throw DeviceOOM(e); // (LM_ERR_NOMEM with the text)
-            for (int64_t l = keep; l < nlocal; l++) {
-                const GenomePlace &pl = plan.place[(size_t)l];
-                HIPCHK(hipMemcpyAsync(ix->g_host_segs[(size_t)pl.seg].p + pl.off, ix->d_gbits.p + goff[(size_t)l], (size_t)nbs[(size_t)(l - keep)],
-                                      hipMemcpyDeviceToHost, ix->st));
-                h.genomes[(size_t)l].bits_off = -1; // (not in the device store)
-                goff[(size_t)l] = -1;
-            }
-            bsync(ix);
-            {   // the device store shrinks to the records that stay (same offsets: they are its first bytes)
-                DBuf<uint8_t> kept;
-                kept.alloc_exact((size_t)kept_bytes + 64, true, ix->st);
-                if (kept_bytes > 0) HIPCHK(hipMemcpyAsync(kept.p, ix->d_gbits.p, (size_t)kept_bytes, hipMemcpyDeviceToDevice, ix->st));
-                bsync(ix);
-                ix->d_gbits.release();
-                std::swap(ix->d_gbits.p, kept.p);
-                std::swap(ix->d_gbits.cap, kept.cap);
-            }
-            copy_up(ix->d_g_off, goff);
-            bsync(ix);
-            ix->view.gbits = ix->d_gbits.p;
-        }
-    }
-    ix->hbm_bytes = ix->seed_bytes + (int64_t)((uint64_t)ix->res.genome_bytes_device + 64 + (uint64_t)M * 8 + pfx.size() * 4 + (uint64_t)nlocal * 20 +
-                                               h.batch_first.size() * 8);
-    lm_set_scratch_budget(ix);
+    // chunks of records: as many as the per-record scratch (16 B per mask) allows in 128 MB, and at most 2^30 bases
+    const int64_t ch_records = std::min<int64_t>(2048, ((int64_t)128 << 20) / ((int64_t)h.M * 16));
+    build_seed_index(ix, b->pfx, b->reg_off, b->reg_s, b->reg_e, bo.max_desert, bo.seed_dist, ch_records, (int64_t)1 << 30, base, nbase, b->rq);
 }
 
 } // namespace lm
@@ -1711,18 +1223,7 @@ lm_status lm_index_builder_new(const lm_build_opt *bo, const lm_options *opt, co
         const lm_status rs = lm_res_resolve(res, rq, g_open_error);
         if (rs != LM_OK) return rs;
     }
-    if (bo->k != 31 || bo->masks < 4 || bo->masks > 65535 || bo->genome_batch_size < 1 || bo->genome_batch_size > (1 << 17) ||
-        bo->max_desert < 1 || bo->seed_dist < 1 || bo->contig_interval < 0 || bo->contig_interval >= (1 << 28) || bo->max_genome >= (1 << 28)) {
-        g_open_error = "lm_index_builder_new: unsupported build options (k must be 31, masks in [4, 65535], genome_batch_size in [1, 2^17], "
-                       "max_desert and seed_dist >= 1, contig_interval >= 0, max_genome < 2^28)";
-        return LM_ERR_ARG;
-    }
-    const int p = std::max(1, (int)(std::log2((double)bo->masks) / 2));
-    if (bo->masks > 2 * (1 << (2 * p))) { // (gen_masks: every p-base prefix once, the rest on distinct prefixes)
-        g_open_error = "lm_index_builder_new: " + std::to_string(bo->masks) + " masks need more than two masks per " + std::to_string(p) +
-                       "-base prefix, which the mask generator of this build does not make (at most " + std::to_string(2 * (1 << (2 * p))) + ")";
-        return LM_ERR_ARG;
-    }
+    if (!build_opt_ok("lm_index_builder_new", *bo, g_open_error)) return LM_ERR_ARG;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
         (void)hipGetLastError();
@@ -1732,48 +1233,15 @@ lm_status lm_index_builder_new(const lm_build_opt *bo, const lm_options *opt, co
     std::unique_ptr<lm_index_builder> b(new lm_index_builder());
     b->bo = *bo;
     b->rq = rq;
-    // measurement / tests only; results do not depend on either
+    // measurement / tests only; results do not depend on it
     if (const char *e = getenv("LM_BUILD_SLAB_KB")) b->slab_bytes = std::max<int64_t>(64, atoll(e)) << 10; // many small slabs
-    if (const char *e = getenv("LM_BUILD_STAGE_SEEDS")) b->stage_seeds = std::max<int64_t>(1024, atoll(e)); // staging arrays that overflow
     try {
         lm_index *ix = new lm_index();
         b->ix = ix;
         ix->opt = *opt;
         ix->device = device;
-        HIPCHK(hipSetDevice(device));
-        HIPCHK(hipStreamCreate(&ix->st));
-        HostIndex &h = ix->host;
-        const int K = bo->k, M = bo->masks;
-        h.k = K;
-        h.M = M;
-        h.main_version = 3;
-        h.minor_version = 5;
-        h.synthetic = false;
-        h.mask_prefix = p;
-        h.anchor_prefix = 6;
-        h.contig_interval = bo->contig_interval;
-        h.shard_rank = opt->shard_count > 1 ? opt->shard_rank : 0;
-        h.shard_count = opt->shard_count > 1 ? opt->shard_count : 1;
-        if (h.shard_rank < 0 || h.shard_rank >= h.shard_count) {
-            g_open_error = "lm_index_builder_new: shard_rank outside [0, shard_count)";
-            return LM_ERR_OPTION;
-        }
-        if (opt->min_prefix > K || opt->min_prefix < p + h.anchor_prefix) {
-            g_open_error = "MinPrefix out of range for this index";
-            return LM_ERR_OPTION;
-        }
-        gen_masks(K, M, (uint64_t)bo->mask_seed, h.masks);
-        b->pfx.assign((size_t)(1ull << (2 * p)) + 1, 0);
-        for (int i = 0; i < M; i++) b->pfx[(size_t)(h.masks[(size_t)i] >> ((K - p) << 1)) + 1]++;
-        for (size_t i = 1; i < b->pfx.size(); i++) {
-            if (b->pfx[i] < 1 || b->pfx[i] > 2) throw HipError("genome builder: the mask set does not have every prefix once or twice");
-            b->pfx[i] += b->pfx[i - 1];
-        }
-        ix->d_masks.ensure((size_t)M);
-        ix->d_pfx_first.ensure(b->pfx.size());
-        HIPCHK(hipMemcpyAsync(ix->d_masks.p, h.masks.data(), (size_t)M * 8, hipMemcpyHostToDevice, ix->st));
-        HIPCHK(hipMemcpyAsync(ix->d_pfx_first.p, b->pfx.data(), b->pfx.size() * 4, hipMemcpyHostToDevice, ix->st));
-        bsync(ix);
+        const lm_status hs = builder_header(ix, bo->k, bo->masks, bo->mask_seed, bo->contig_interval, nullptr, b->pfx);
+        if (hs != LM_OK) return hs;
     } catch (const std::exception &e) {
         g_open_error = e.what();
         return LM_ERR_HIP;
@@ -1781,7 +1249,6 @@ lm_status lm_index_builder_new(const lm_build_opt *bo, const lm_options *opt, co
     *out = b.release();
     return LM_OK;
 }
-
 // A builder that continues a resident index ("Adding genomes to a resident index").  Everything per record -
 // key, captures, desert seeds, reversed seeds - is a function of the record and its number alone, and the packer takes seeds
 // in any order: so the base's seeds are decoded from its image (k_sp_dump_range), the added records are captured, and finish()
@@ -1823,12 +1290,7 @@ lm_status lm_index_builder_extend(lm_index *base, const lm_build_opt *bo_in, con
     bo.mask_seed = bh.rand_seed; // (the masks are the base's, whatever seed made them)
     bo.contig_interval = bh.contig_interval;
     bo.genome_batch_size = bh.genome_batch_size;
-    if (bo.k != 31 || bo.masks < 4 || bo.masks > 65535 || bo.genome_batch_size < 1 || bo.genome_batch_size > (1 << 17) || bo.max_desert < 1 ||
-        bo.seed_dist < 1 || bo.contig_interval < 0 || bo.contig_interval >= (1 << 28) || bo.max_genome >= (1 << 28)) {
-        g_open_error = "lm_index_builder_extend: unsupported settings (k must be 31, masks in [4, 65535], genome_batch_size in [1, 2^17], "
-                       "max_desert and seed_dist >= 1, contig_interval >= 0, max_genome < 2^28)";
-        return LM_ERR_ARG;
-    }
+    if (!build_opt_ok("lm_index_builder_extend", bo, g_open_error)) return LM_ERR_ARG;
     if (bh.synthetic && bh.shard_count > 1) {
         g_open_error = "lm_index_builder_extend: a shard of a synthetic set cannot be continued (its records are numbered without a table)";
         return LM_ERR_ARG;
@@ -1851,7 +1313,6 @@ lm_status lm_index_builder_extend(lm_index *base, const lm_build_opt *bo_in, con
         g_open_error = "lm_index_builder_extend: the record tables of the index do not agree with its batches";
         return LM_ERR_ARG;
     }
-    const int K = bh.k, M = bh.M, p = bh.mask_prefix;
     std::unique_ptr<lm_index_builder> b(new lm_index_builder());
     b->bo = bo;
     b->rq = rq;
@@ -1862,41 +1323,17 @@ lm_status lm_index_builder_extend(lm_index *base, const lm_build_opt *bo_in, con
     b->ninput = bh.input_genomes > 0 ? bh.input_genomes : base_records;
     b->input_bases = bh.total_bases;
     if (const char *e = getenv("LM_BUILD_SLAB_KB")) b->slab_bytes = std::max<int64_t>(64, atoll(e)) << 10;
-    if (const char *e = getenv("LM_BUILD_STAGE_SEEDS")) {
-        b->piece_seeds = std::max<int64_t>(4, atoll(e)); // (the decode pieces may be smaller than what a capture needs)
-        b->stage_seeds = std::max<int64_t>(1024, atoll(e));
-    }
-    b->pfx.assign((size_t)(1ull << (2 * p)) + 1, 0);
-    for (int i = 0; i < M; i++) b->pfx[(size_t)(bh.masks[(size_t)i] >> ((K - p) << 1)) + 1]++;
-    for (size_t i = 1; i < b->pfx.size(); i++) {
-        if (b->pfx[i] < 1 || b->pfx[i] > 2) {
-            g_open_error = "lm_index_builder_extend: the mask set of the index does not have every " + std::to_string(p) + "-base prefix once or twice";
-            return LM_ERR_ARG;
-        }
-        b->pfx[i] += b->pfx[i - 1];
-    }
     try {
         lm_index *ix = new lm_index();
         b->ix = ix;
         ix->opt = base->opt;
         ix->device = base->device;
-        HIPCHK(hipSetDevice(ix->device));
-        HIPCHK(hipStreamCreate(&ix->st));
+        const lm_status hs = builder_header(ix, bh.k, bh.M, bh.rand_seed, bh.contig_interval, &bh, b->pfx);
+        if (hs != LM_OK) return hs;
         HostIndex &h = ix->host;
-        h.k = K;
-        h.M = M;
-        h.main_version = 3;
-        h.minor_version = 5;
-        h.synthetic = false;
-        h.mask_prefix = p;
-        h.anchor_prefix = bh.anchor_prefix;
-        h.contig_interval = bh.contig_interval;
-        h.shard_rank = bh.shard_rank;
-        h.shard_count = bh.shard_count;
         h.rand_seed = bh.rand_seed;
         h.max_seed_dist = bh.max_seed_dist;
         h.seed_dist_in_desert = bh.seed_dist_in_desert;
-        h.masks = bh.masks;
         // the base's tables in front: add() appends to them as it does in a fresh builder
         h.genomes = bh.genomes;
         h.others = bh.others;
@@ -1911,11 +1348,6 @@ lm_status lm_index_builder_extend(lm_index *base, const lm_build_opt *bo_in, con
             b->store_bytes += build_slot_bytes(G.len);
             b->max_len = std::max<int64_t>(b->max_len, G.len);
         }
-        ix->d_masks.ensure((size_t)M);
-        ix->d_pfx_first.ensure(b->pfx.size());
-        HIPCHK(hipMemcpyAsync(ix->d_masks.p, h.masks.data(), (size_t)M * 8, hipMemcpyHostToDevice, ix->st));
-        HIPCHK(hipMemcpyAsync(ix->d_pfx_first.p, b->pfx.data(), b->pfx.size() * 4, hipMemcpyHostToDevice, ix->st));
-        bsync(ix);
     } catch (const std::exception &e) {
         g_open_error = e.what();
         return LM_ERR_HIP;
@@ -2038,7 +1470,7 @@ lm_status lm_index_builder_finish(lm_index_builder *bp, lm_index **out) {
     if (b->base) base_lock = std::unique_lock<std::mutex>(b->base->mu);
     try {
         HIPCHK(hipSetDevice(b->ix->device));
-        builder_finish(b.get(), b->rq);
+        builder_finish(b.get());
     } catch (const DeviceOOM &e) {
         g_open_error = e.what();
         if (b->base)
@@ -2057,5 +1489,123 @@ lm_status lm_index_builder_finish(lm_index_builder *bp, lm_index **out) {
 void lm_index_builder_free(lm_index_builder *b) { delete b; }
 
 const char *lm_index_builder_last_error(const lm_index_builder *b) { return b ? b->err.c_str() : g_open_error.c_str(); }
+
+lm_status lm_index_build_synthetic(const lm_synth_spec *spec, const lm_options *opt, int device, lm_index **out) {
+    return lm_index_build_synthetic_ex(spec, opt, nullptr, device, out);
+}
+// The synthetic front end: the genomes of this shard written straight into one store (no slabs: the peak of a build is the
+// store + the staging of one chunk), their names and keys; the records of a sharded set are numbered without a table
+// (h.g2local stays empty).  Chunks of 2048 records whatever their length: at 5 Mb per genome that is eight full rounds of one
+// workgroup per CU, where a bound on the bases would leave CUs idle and multiply the host synchronisations.
+lm_status lm_index_build_synthetic_ex(const lm_synth_spec *spec, const lm_options *opt, const lm_residency *res, int device, lm_index **out) {
+    *out = nullptr;
+    lm_res_request rq;
+    {
+        const lm_status rs = lm_res_resolve(res, rq, g_open_error);
+        if (rs != LM_OK) return rs;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
+        g_open_error = "no HIP device available (this library has no CPU path)";
+        return LM_ERR_NO_DEVICE;
+    }
+    if (!seed_settings_ok("lm_index_build_synthetic", spec->k, spec->masks, spec->max_desert, spec->seed_dist, g_open_error)) return LM_ERR_ARG;
+    if (spec->genome_len < 64 || spec->genomes < 1 || spec->genome_len >= (1 << 28) || spec->families < 1) {
+        g_open_error = "lm_index_build_synthetic: unsupported spec (genome_len in [64, 2^28), genomes and families >= 1)";
+        return LM_ERR_ARG;
+    }
+    lm_index *ix = new lm_index();
+    try {
+        ix->opt = *opt;
+        ix->device = device;
+        std::vector<int32_t> pfx;
+        const lm_status hs = builder_header(ix, spec->k, spec->masks, spec->mask_seed, 1000, nullptr, pfx);
+        if (hs != LM_OK) {
+            delete ix;
+            return hs;
+        }
+        HostIndex &h = ix->host;
+        h.synthetic = true;
+        h.synth_genome_len = spec->genome_len;
+        h.synth_genomes = spec->genomes;
+        h.total_bases = opt->total_bases_override > 0 ? opt->total_bases_override : spec->genomes * (int64_t)spec->genome_len;
+        h.genome_batches = (int)((spec->genomes + 4999) / 5000);
+        h.batch_first.assign(h.genome_batches + 1, 0);
+        for (int b = 0; b <= h.genome_batches; b++) h.batch_first[b] = std::min<int64_t>((int64_t)b * 5000, spec->genomes);
+        // local genomes
+        int64_t nlocal = 0;
+        for (int64_t g = 0; g < spec->genomes; g++)
+            if ((int)(g % h.shard_count) == h.shard_rank) nlocal++;
+        SynthDev sp;
+        sp.seed = (uint64_t)spec->seed;
+        sp.genomes = spec->genomes;
+        sp.genome_len = spec->genome_len;
+        sp.families = (int32_t)std::min<int64_t>(spec->families, spec->genomes);
+        sp.max_div = spec->max_div;
+        sp.shard_rank = h.shard_rank;
+        sp.shard_count = h.shard_count;
+        sp.nlocal = nlocal;
+        sp.nblk = (spec->genome_len + 511) >> 9;
+        sp.gbytes = build_slot_bytes(spec->genome_len);
+        ix->d_gbits.alloc_exact((size_t)(nlocal * sp.gbytes) + 64);
+        HIPCHK(hipMemsetAsync(ix->d_gbits.p, 0, (size_t)(nlocal * sp.gbytes) + 64, ix->st));
+        DBuf<int16_t> shifts;
+        shifts.ensure((size_t)(nlocal * sp.nblk) + 1);
+        hipLaunchKernelGGL(k_synth_shifts, dim3(gridn(nlocal, 64)), dim3(64), 0, ix->st, sp, shifts.p);
+        hipLaunchKernelGGL(k_synth_genomes, dim3(gridn(nlocal * (((int64_t)spec->genome_len + 3) >> 2))), dim3(256), 0, ix->st,
+                           sp, shifts.p, ix->d_gbits.p);
+        bsync(ix);
+        shifts.release();
+        h.genomes.resize(nlocal);
+        for (int64_t l = 0; l < nlocal; l++) {
+            int64_t g = h.shard_count > 1 ? l * h.shard_count + h.shard_rank : l;
+            HostGenome &G = h.genomes[l];
+            G.bg = build_genome_key(g, 5000);
+            G.global = g;
+            char nm[64];
+            snprintf(nm, sizeof nm, "SYN_%09lld.1", (long long)g);
+            G.id = nm;
+            G.genome_size = spec->genome_len;
+            G.len = spec->genome_len;
+            G.nseqs = 1;
+            G.seq_sizes = {spec->genome_len};
+            snprintf(nm, sizeof nm, "syn%09lld_c1", (long long)g);
+            G.seq_ids = {std::string(nm)};
+            G.bits_off = l * sp.gbytes;
+        }
+        const std::vector<int32_t> no_regions((size_t)nlocal + 1, 0);
+        build_seed_index(ix, pfx, no_regions, {}, {}, spec->max_desert, spec->seed_dist, 2048, INT64_MAX, nullptr, 0, rq);
+    } catch (const PinnedOOM &e) {
+        g_open_error = e.what();
+        delete ix;
+        return LM_ERR_NOMEM;
+    } catch (const std::exception &e) {
+        g_open_error = e.what();
+        delete ix;
+        return LM_ERR_HIP;
+    }
+    *out = ix;
+    return LM_OK;
+}
+lm_status lm_index_fetch(lm_index *ix, int64_t local_genome, int64_t start, int64_t len, uint8_t *out) {
+    if (!ix || local_genome < 0 || local_genome >= (int64_t)ix->host.genomes.size()) return LM_ERR_ARG;
+    const HostGenome &G = ix->host.genomes[local_genome];
+    if (start < 0 || len < 0 || start + len > G.len) return LM_ERR_ARG;
+    try {
+        std::lock_guard<std::mutex> lock(ix->mu);
+        HIPCHK(hipSetDevice(ix->device));
+        DBuf<uint8_t> d;
+        d.ensure((size_t)len + 1);
+        // (a host-resident genome is read where it lives: this kernel and k_stage_genome_bits are the two that may)
+        const uint8_t *gsrc = !ix->g_hptr.empty() && ix->g_hptr[(size_t)local_genome] ? ix->g_hptr[(size_t)local_genome] : ix->d_gbits.p + G.bits_off;
+        hipLaunchKernelGGL(k_fetch_bases, dim3(gridn(len)), dim3(256), 0, ix->st, gsrc, start, len, d.p);
+        HIPCHK(hipMemcpyAsync(out, d.p, (size_t)len, hipMemcpyDeviceToHost, ix->st));
+        bsync(ix);
+    } catch (const std::exception &e) {
+        ix->err = e.what();
+        return LM_ERR_HIP;
+    }
+    return LM_OK;
+}
 
 } // extern "C"

@@ -161,3 +161,120 @@ def test_seed_density_like_reference_builder(synth_index):
     per_genome = info["seeds"] / info["genomes"]
     expect = 2 * (20000 * 0.9 + 0.8 * 200_000 / 50)
     assert 0.6 * expect < per_genome < 1.6 * expect, per_genome
+
+
+def _sampled_lists(gi, sample):
+    out = {}
+    for m in sample:
+        k, v = gi.mask_seeds(m)
+        out[m] = sorted(zip(k.tolist(), v.tolist()))
+    return out
+
+
+def test_short_genomes_take_the_missing_prefix_rule(tmp_path):
+    """20-kb genomes leave about exp(-2 * 19 970 / 16 384) = 8.7 % of the 16 384 7-base prefixes without a k-mer of either
+    strand: a mask on such a prefix captures the argmin over ALL k-mers of the genome (MaskKnownDistinctPrefixes(...,
+    checkShorterPrefix = true)), as the oracle's writer does - every sampled list is the writer's, and masks of that kind
+    are among the sampled ones and hold captures"""
+    import lexicmap_amd as la
+    L = 20_000
+    gi = la.Index.synthetic(genomes=4, genome_len=L, families=2, seed=77)
+    try:
+        M = gi.info()["masks"]
+        assert M == 20_000 and gi.info()["mask_prefix"] == 7
+        masks_p = la.lib().lm_index_masks(gi.h)
+        masks = [masks_p[i] for i in range(M)]
+        seqs = [gi.fetch(g, 0, L) for g in range(4)]
+        d = str(tmp_path / "short.lmi")
+        O.build_index(d, [("SYN_%09d.1" % g, [("syn%09d_c1" % g, seqs[g])]) for g in range(4)], O.default_build_opt(chunks=4), masks=masks)
+        oi = la.Index(d)
+        try:
+            assert oi.info()["seeds"] == gi.info()["seeds"]
+            sample = list(range(0, M, 7)) + [M - 1]
+            got = _sampled_lists(gi, sample)
+            exp = _sampled_lists(oi, sample)
+            for m in sample:
+                a, b = got[m], exp[m]
+                assert a == b, (m, len(a), len(b), [x for x in a if x not in b][:3], [x for x in b if x not in a][:3])
+        finally:
+            oi.close()
+        # the 7-base prefixes of the k-mers of both strands of genome 0: the 7-mers that start a 31-mer, and the reverse
+        # complements of those that end one
+        code = np.zeros(256, dtype=np.int64)
+        for i, ch in enumerate(b"ACGT"):
+            code[ch] = i
+        c = code[np.frombuffer(seqs[0], dtype=np.uint8)]
+        n7 = L - 6
+        fwd = sum(c[j:j + n7] << (2 * (6 - j)) for j in range(7))
+        rc = sum((3 - c[6 - j:6 - j + n7]) << (2 * (6 - j)) for j in range(7))
+        present = np.zeros(1 << 14, dtype=bool)
+        present[fwd[:L - 30]] = True
+        present[rc[24:]] = True
+        missing = [m for m in sample if not present[masks[m] >> 48]]
+        assert len(missing) >= 0.02 * len(sample), (len(missing), len(sample))
+        # captured all the same: a normal (not reversed) seed of genome 0 under such a mask can only come from the rule
+        assert any((v >> 30) == 0 and not v & 1 for m in missing for _, v in got[m])
+    finally:
+        gi.close()
+
+
+@pytest.fixture(scope="module")
+def synth6():
+    import lexicmap_amd as la
+    gi = la.Index.synthetic(genomes=6, genome_len=120_000, families=2, seed=77)
+    sample = list(range(0, 20_000, 7)) + [19_999]
+    yield {"seeds": gi.info()["seeds"], "sample": sample, "lists": _sampled_lists(gi, sample)}
+    gi.close()
+
+
+def test_sharded_synthetic_set_holds_its_share_of_every_list(synth6):
+    """rank r of two keeps the genomes l * 2 + r, numbered without a table: every sampled list is the unsharded build's list
+    restricted to the values of genomes of that parity (one batch: the genome number is v >> 30)"""
+    import lexicmap_amd as la
+    seeds = 0
+    for rank in (0, 1):
+        gi = la.Index.synthetic(genomes=6, genome_len=120_000, families=2, seed=77,
+                                options=la.api.default_options(shard_rank=rank, shard_count=2))
+        try:
+            assert gi.info()["genomes"] == 3
+            seeds += gi.info()["seeds"]
+            got = _sampled_lists(gi, synth6["sample"])
+            for m in synth6["sample"]:
+                assert got[m] == [kv for kv in synth6["lists"][m] if (kv[1] >> 30) % 2 == rank], (rank, m)
+        finally:
+            gi.close()
+    assert seeds == synth6["seeds"]
+
+
+def test_settings_the_pipeline_cannot_honour_are_refused():
+    """3000 masks would need more than two masks on some 5-base prefix (the mask generator makes at most 2 x 4^5), and a
+    desert walk with seed_dist = 0 never advances: LM_ERR_ARG with a text, and the next build is not affected"""
+    import lexicmap_amd as la
+    L = la.lib()
+    opt = la.api.default_options()
+    for masks, seed_dist in ((3000, 50), (20_000, 0)):
+        sp = la.api.SynthSpec(31, masks, 1, 4, 120_000, 2, 0.10, 77, 100, seed_dist)
+        h = C.c_void_p()
+        assert L.lm_index_build_synthetic(C.byref(sp), C.byref(opt), 0, C.byref(h)) == 7 and not h.value   # LM_ERR_ARG
+        assert L.lm_last_error(None)
+    gi = la.Index.synthetic(genomes=2, genome_len=20_000, families=1, seed=77, masks=1024)
+    try:
+        assert gi.info()["genomes"] == 2 and gi.info()["seeds"] > 0
+    finally:
+        gi.close()
+
+
+def test_staging_arrays_that_overflow_are_enlarged_on_the_synthetic_path(synth6, monkeypatch, capfd):
+    """staging arrays of 4096 seeds overflow in the capture of 6 x 120 kb: the chunk is generated again into larger ones, to
+    the same index"""
+    import lexicmap_amd as la
+    monkeypatch.setenv("LM_BUILD_STAGE_SEEDS", "4096")
+    monkeypatch.setenv("LM_DEBUG", "1")
+    capfd.readouterr()
+    gi = la.Index.synthetic(genomes=6, genome_len=120_000, families=2, seed=77)
+    try:
+        assert "staging buffers enlarged" in capfd.readouterr().err
+        assert gi.info()["seeds"] == synth6["seeds"]
+        assert _sampled_lists(gi, synth6["sample"]) == synth6["lists"]
+    finally:
+        gi.close()
