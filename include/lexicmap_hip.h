@@ -144,8 +144,9 @@ lm_status lm_index_get_residency(const lm_index *idx, lm_residency_info *info);
  *   lm_index_builder_finish: captures (LexicHash, with the masks-without-a-matching-prefix rule), seed-desert filling, reversed
  *     seeds, packed seed image; `res` of _new is honoured as by lm_index_build_synthetic_ex.  The builder is consumed whether
  *     finish succeeds or not; after a failure lm_last_error(NULL) has the text.  LM_ERR_ARG when nothing was added.
- * Not done here (nor by the reference at this point): reading FASTA / gz files, soft-masking, --max-kmer-freq, merging
- * two finished indexes (genomes are ADDED to a resident one by lm_index_builder_extend); k must be 31 and the mask set may have at most two masks per p-base prefix (masks <= 2 * 4^p). */
+ * Not done here (nor by the reference at this point): reading FASTA / gz files, soft-masking, --max-kmer-freq (genomes are
+ * ADDED to a resident index by lm_index_builder_extend, resident indexes are joined and subset by
+ * lm_index_builder_add_index; joining SHARDS is not done); k must be 31 and the mask set may have at most two masks per p-base prefix (masks <= 2 * 4^p). */
 typedef struct lm_build_opt {      /* lm_build_opt_default(): the defaults of `lexicmap index` (index.go:538-619) */
     int32_t k;                     /* 31 (only 31 is accepted, as in lm_index_build_synthetic) */
     int32_t masks;                 /* 20000; [4, 65535] with at most two masks per p-base prefix, p = max(1, floor(log4 masks)):
@@ -185,6 +186,38 @@ const char *lm_index_builder_last_error(const lm_index_builder *b);
  *   base's image, the new image and the seed staging arrays are on the device together; LM_ERR_NOMEM (base intact, the
  *     builder consumed) when they do not fit. */
 lm_status lm_index_builder_extend(lm_index *base, const lm_build_opt *bo, const lm_residency *res, lm_index_builder **out);
+/* Appends the genome records of a resident index to the builder, in src's record order, numbered on from the builder's
+ * record count: what _add of those genomes, in that order, would have appended - without capturing them again.  finish()
+ * copies their 2-bit records, decodes their seeds from src's image, gives them the new keys and packs them with the rest.
+ * keep == NULL: all records.  Otherwise keep[0..nkeep) are record keys of src (batch << 17 | index, as
+ * lm_index_set_genome_filter takes them); only those records are appended, still in src's order.
+ *   _add and _add_index may be called in any order and any number of times on a builder of _new, _extend or _like: join
+ *     (_extend(A), _add_index(B)), N-way join, subset (_like(A), _add_index(A, keep)), and genomes added in between.
+ *   Preconditions, each refused with LM_ERR_ARG and a text (lm_index_builder_last_error) that names what differs; nothing is
+ *     added and the builder stays usable: src and the builder agree in k, in contig_interval, in the number of masks and in
+ *     the mask VALUES (two sets of as many masks from different seeds are different masks); both are on the same device; both
+ *     are unsharded (shard_count == 1: joining shards would move records between ranks); src is not the builder's base and
+ *     was not added to this builder before.
+ *   Keep list, LM_ERR_ARG likewise: a key that is no record of src; a key given twice; a genome that was split into several
+ *     records (genomes.chunks.bin) named with some of its records but not all; an empty selection (keep != NULL, nkeep == 0).
+ *   src's batch layout does not matter, every record is renumbered: an index with irregular batches, which _extend refuses
+ *     as a base, is a legal source.
+ *   Every appended record is a copy of src's (genome id, contig ids and sizes, genome size, length) under its new key; chunk
+ *     lists keep their shape under new list numbers; the input-genome count grows by the genomes appended (a split genome
+ *     counts once), the input bases by their genome sizes.  lm_index_get_info and lm_index_save of the result equal those of
+ *     one build of the same genomes in the same order.  max-seed-dist and seed-dist-in-desert of the result are the
+ *     builder's: those of a source are NOT checked, its deserts were filled when it was built.
+ *   src is only read.  It must stay open until finish or free has returned; finish holds the locks of the base and of every
+ *     source while it reads (taken in the order of the handles' addresses).  Sources stay open, unchanged and searchable; a
+ *     source's genome filter is not carried.
+ *   The sources, the new store, the new image and the seed staging arrays are on the device together; LM_ERR_NOMEM (sources
+ *     intact, the builder consumed, the text says so) when they do not fit.  Sources are not released as they are consumed. */
+lm_status lm_index_builder_add_index(lm_index_builder *b, lm_index *src, const uint64_t *keep, size_t nkeep);
+/* An empty builder with the masks, lm_options, device and build settings of `model` (nothing of its genomes): what _extend
+ * gives, minus the base.  bo / res as in _extend, with the same refusals for a bo that disagrees with model in k, masks,
+ * contig_interval or genome_batch_size; model's batches need not be regular, since nothing is continued.  model is only
+ * read, and only during this call.  finish with nothing added stays LM_ERR_ARG. */
+lm_status lm_index_builder_like(const lm_index *model, const lm_build_opt *bo, const lm_residency *res, lm_index_builder **out);
 /* bases [start, start+len) of local genome `local_genome` as ASCII (used to derive synthetic queries) */
 lm_status lm_index_fetch(lm_index *idx, int64_t local_genome, int64_t start, int64_t len, uint8_t *out);
 /* Writes the resident (unsharded) index to `dir`: info.toml, seeds/chunk_NNN.bin (+ .idx, kv/kv-data.go:126-602) in at most

@@ -158,6 +158,8 @@ def lib():
     L.lm_build_opt_default.restype = None
     L.lm_index_builder_new.argtypes = [C.POINTER(BuildOpt), C.POINTER(Options), C.POINTER(Residency), C.c_int, C.POINTER(vp)]
     L.lm_index_builder_extend.argtypes = [vp, C.POINTER(BuildOpt), C.POINTER(Residency), C.POINTER(vp)]
+    L.lm_index_builder_like.argtypes = [vp, C.POINTER(BuildOpt), C.POINTER(Residency), C.POINTER(vp)]
+    L.lm_index_builder_add_index.argtypes = [vp, vp, C.POINTER(C.c_uint64), C.c_size_t]
     L.lm_index_builder_add.argtypes = [vp, C.c_char_p, C.POINTER(Contig), C.c_size_t]
     L.lm_index_builder_finish.argtypes = [vp, C.POINTER(vp)]
     L.lm_index_builder_free.argtypes = [vp]
@@ -318,6 +320,30 @@ class Index:
         try:
             for gid, contigs in genomes:
                 b.add(gid, contigs)
+            return b.finish()
+        finally:
+            b.close()
+
+    def join(self, *others, build_opt=None, residency=None):
+        """a NEW Index holding this one's genomes followed by those of every Index in `others`, in that order
+        (lm_index_builder_extend + lm_index_builder_add_index): what one from_genomes build of all of them gives, without
+        capturing any genome again.  All inputs share this index's masks, k and contig interval, are unsharded and on one
+        device; they stay open and unchanged.  build_opt and residency as in extend."""
+        b = IndexBuilder.extending(self, build_opt, residency)
+        try:
+            for o in others:
+                b.add_index(o)
+            return b.finish()
+        finally:
+            b.close()
+
+    def subset(self, keep_keys, build_opt=None, residency=None):
+        """a NEW Index holding the records of this one whose keys (batch << 17 | index) are in keep_keys, in this index's
+        order and numbered from 0 (lm_index_builder_like + lm_index_builder_add_index): what one from_genomes build of those
+        genomes gives.  A split genome is kept with all of its records or none.  self stays open and unchanged."""
+        b = IndexBuilder.like(self, build_opt, residency)
+        try:
+            b.add_index(self, keep_keys)
             return b.finish()
         finally:
             b.close()
@@ -655,8 +681,50 @@ class IndexBuilder:
         self.h = h
         return self
 
+    @classmethod
+    def like(cls, index, build_opt=None, residency=None):
+        """lm_index_builder_like: an empty builder with the masks, options, device and build settings of `index`"""
+        L = lib()
+        self = cls.__new__(cls)
+        self.opt = index.opt
+        self.bo = build_opt
+        self.device = 0
+        h = C.c_void_p()
+        st = L.lm_index_builder_like(index.h, C.byref(build_opt) if build_opt is not None else None,
+                                     C.byref(residency) if residency is not None else None, C.byref(h))
+        if st != 0:
+            e = RuntimeError("lm_index_builder_like failed (%d): %s" % (st, L.lm_last_error(None).decode()))
+            e.status = st
+            raise e
+        self.h = h
+        return self
+
     def last_error(self):
         return lib().lm_index_builder_last_error(self.h).decode()
+
+    def try_add_index(self, index, keep=None):
+        """lm_index_builder_add_index: the status (0 = appended; 7 = LM_ERR_ARG: refused, see last_error(), the builder stays
+        usable).  keep: record keys (batch << 17 | index) of `index`, None for all of its records."""
+        if keep is None:
+            arr, n = None, 0
+        else:
+            keys = [int(k) for k in keep]
+            n = len(keys)
+            arr = (C.c_uint64 * max(n, 1))(*keys)
+        st = lib().lm_index_builder_add_index(self.h, index.h, arr, n)
+        if st == 0:
+            if not hasattr(self, "sources"):
+                self.sources = []
+            self.sources.append(index)  # (kept alive for as long as the builder reads it)
+        return st
+
+    def add_index(self, index, keep=None):
+        st = self.try_add_index(index, keep)
+        if st == 7:
+            raise ValueError(self.last_error())
+        if st != 0:
+            raise RuntimeError("lm_index_builder_add_index failed (%d): %s" % (st, self.last_error()))
+        return self
 
     def try_add(self, genome_id, contigs):
         """lm_index_builder_add: the status (0 = added; 7 = LM_ERR_ARG: refused, see last_error(), the builder stays usable)"""

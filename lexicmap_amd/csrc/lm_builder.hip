@@ -28,6 +28,7 @@
 #include "lm_internal.h"
 #include "lm_prims.h"
 #include "lm_build_plan.h"
+#include "lm_join_plan.h"
 
 namespace lm {
 
@@ -661,10 +662,21 @@ struct lm_index_builder {
     };
     std::vector<std::unique_ptr<Slab>> slabs;
     int64_t slab_bytes = (int64_t)256 << 20, store_bytes = 0;
-    // lm_index_builder_extend: the index this builder continues (borrowed, only read), how many of ix->host.genomes are its
-    // local records (they lie in front, their store slots planned but not filled before finish) and its record count over all shards
+    // lm_index_builder_extend: the index this builder continues (borrowed, only read) and its record count over all shards
     lm_index *base = nullptr;
-    int64_t nbase = 0, base_records = 0;
+    int64_t base_records = 0;
+    // Resident indexes whose records this builder borrows (only read): the base, all of its local records under their own keys
+    // (new_bg empty), then one entry per lm_index_builder_add_index.  recs: (local record there, local record here); the store
+    // slots here are planned when the records are appended and filled by finish.  borrowed[l]: record l of ix->host.genomes
+    // is one of them - its seeds are decoded from the source's image, not captured.
+    struct Source {
+        lm_index *ix = nullptr;
+        std::vector<uint64_t> new_bg; // [the source's local records] key here or JOIN_DROP (lm_join_plan.h)
+        bool drops = false;
+        std::vector<std::pair<int64_t, int64_t>> recs;
+    };
+    std::vector<Source> sources;
+    std::vector<uint8_t> borrowed;
     std::vector<int32_t> reg_off{0}, reg_s, reg_e; // skip regions of the local records (CSR)
     std::vector<int32_t> g2local;                  // sharded: record number -> local number or -1
     std::vector<int32_t> pfx;
@@ -814,11 +826,20 @@ static lm_status builder_header(lm_index *ix, int K, int M, int64_t mask_seed, i
 // seeds of the whole set never exist (they would not fit beside the packed image at BASELINE configs 3-5).  A chunk holds
 // at most chunk_records records and chunk_bases bases - the caller's choice: a record of a chunk costs 16 B x masks of
 // scratch (24 B with the minima in a global table), a chunk one host synchronisation per phase.
-// reg_off / reg_s / reg_e: CSR of the skip regions of every record (all zeros: none).  base, nbase: the records [0, nbase)
-// are those of the resident index `base`; their seeds are decoded from its image, not captured again.
+// reg_off / reg_s / reg_e: CSR of the skip regions of every record (all zeros: none).  The record list is a sequence of runs
+// that are either captured or borrowed from a resident index (borrowed[l] != 0; empty: every record is captured): the seeds
+// of a borrowed record are decoded from the image of its source - `sources`, in the order their records come - and given
+// the record's key here (SeedSource::new_bg; null: the source's own keys, the base of lm_index_builder_extend).  Capture
+// chunks are cut from captured runs only, and a borrowed record has no skip regions.
+struct SeedSource {
+    const lm_index *ix;
+    const std::vector<uint64_t> *new_bg; // null or [ix's local records]: lm_join_plan.h
+    bool drops;                          // some entry is JOIN_DROP: the decode compacts
+    const char *what;                    // LM_DEBUG: "the base" / "source N"
+};
 static void build_seed_index(lm_index *ix, const std::vector<int32_t> &pfx, const std::vector<int32_t> &reg_off, const std::vector<int32_t> &reg_s,
                              const std::vector<int32_t> &reg_e, int max_desert, int seed_dist, int64_t chunk_records, int64_t chunk_bases,
-                             const lm_index *base, int64_t nbase, const lm_res_request &rq) {
+                             const std::vector<SeedSource> &sources, const std::vector<uint8_t> &borrowed, const lm_res_request &rq) {
     HostIndex &h = ix->host;
     const int K = h.k, M = h.M, p = h.mask_prefix;
     const int64_t nlocal = (int64_t)h.genomes.size();
@@ -904,11 +925,16 @@ static void build_seed_index(lm_index *ix, const std::vector<int32_t> &pfx, cons
         int n;
         double seeds, pos;
     };
-    std::vector<Chunk> chunks; // (of the added records only)
-    for (int64_t l = nbase; l < nlocal;) {
+    std::vector<Chunk> chunks; // (of the captured records only: a chunk never reaches across a borrowed run)
+    auto is_borrowed = [&](int64_t l) { return !borrowed.empty() && borrowed[(size_t)l] != 0; };
+    for (int64_t l = 0; l < nlocal;) {
+        if (is_borrowed(l)) {
+            l++;
+            continue;
+        }
         Chunk c{l, 0, 0, 0};
         int64_t bases = 0;
-        while (l < nlocal && c.n < ch_max && (c.n == 0 || bases + glen[(size_t)l] <= chunk_bases)) {
+        while (l < nlocal && !is_borrowed(l) && c.n < ch_max && (c.n == 0 || bases + glen[(size_t)l] <= chunk_bases)) {
             bases += glen[(size_t)l];
             c.seeds += 2.0 * (1.45 * M + (double)glen[(size_t)l] / 42.0) + 1024;
             c.pos += 1.45 * M + 64;
@@ -925,18 +951,28 @@ static void build_seed_index(lm_index *ix, const std::vector<int32_t> &pfx, cons
         est_pos = std::max(est_pos, c.pos);
     }
     unsigned long long cap = (unsigned long long)est_seeds + 65536, pos_cap = (unsigned long long)est_pos + (unsigned long long)ch_n + 64;
-    // the base's seeds pass through the same arrays in pieces: large enough that a big image is not cut into thousands of launches
-    std::vector<int64_t> base_md_off, base_out_off;
-    int64_t base_main = 0, base_out = 0;
-    if (base) {
-        base_md_off.resize((size_t)2 * M + 1);
-        base_out_off.resize((size_t)2 * M + 1);
-        HIPCHK(hipMemcpyAsync(base_md_off.data(), base->d_md_off.p, base_md_off.size() * 8, hipMemcpyDeviceToHost, ix->st));
-        HIPCHK(hipMemcpyAsync(base_out_off.data(), base->d_out_off.p, base_out_off.size() * 8, hipMemcpyDeviceToHost, ix->st));
+    // the sources' seeds pass through the same arrays in pieces: large enough that a big image is not cut into thousands of launches
+    struct SrcTabs {
+        std::vector<int64_t> md_off, out_off;
+        int64_t n_main = 0, n_out = 0;
+        DBuf<uint64_t> new_bg;
+    };
+    std::vector<std::unique_ptr<SrcTabs>> stabs;
+    for (const SeedSource &S : sources) {
+        std::unique_ptr<SrcTabs> t(new SrcTabs());
+        t->md_off.resize((size_t)2 * M + 1);
+        t->out_off.resize((size_t)2 * M + 1);
+        HIPCHK(hipMemcpyAsync(t->md_off.data(), S.ix->d_md_off.p, t->md_off.size() * 8, hipMemcpyDeviceToHost, ix->st));
+        HIPCHK(hipMemcpyAsync(t->out_off.data(), S.ix->d_out_off.p, t->out_off.size() * 8, hipMemcpyDeviceToHost, ix->st));
+        if (S.new_bg) {
+            if ((int64_t)S.new_bg->size() != S.ix->view.ngenomes) throw HipError("index build: a source's key table does not match its records");
+            copy_up(t->new_bg, *S.new_bg);
+        }
         bsync(ix);
-        base_main = base_md_off.back();
-        base_out = base_out_off.back();
-        cap = std::max<unsigned long long>(cap, (unsigned long long)std::min<int64_t>(std::max(base_main, base_out), (int64_t)1 << 26));
+        t->n_main = t->md_off.back();
+        t->n_out = t->out_off.back();
+        cap = std::max<unsigned long long>(cap, (unsigned long long)std::min<int64_t>(std::max(t->n_main, t->n_out), (int64_t)1 << 26));
+        stabs.push_back(std::move(t));
     }
     if (stage_seeds > 0) { // (tests: a first estimate that is too small, so that the enlarge-and-retry path runs)
         cap = (unsigned long long)stage_seeds;
@@ -1016,21 +1052,37 @@ static void build_seed_index(lm_index *ix, const std::vector<int32_t> &pfx, cons
     };
     double t_base = 0, t_dump = 0;
     for (int pass = 0; pass < 2; pass++) {
-        if (base) {
-            // the base's seeds first, decoded in pieces no larger than the staging arrays (a list longer than a piece is cut);
-            // every value is re-encoded by the packer: gid_bits / pos_bits of the extended set may be wider than the base's
+        for (size_t si = 0; si < sources.size(); si++) {
+            // a source's seeds, decoded in pieces no larger than the staging arrays (a list longer than a piece is cut); every
+            // value is re-encoded by the packer: gid_bits / pos_bits of the new set may be wider than the source's.  Where the
+            // source keeps only some of its records the kernel compacts and the host reads the piece's count (8 bytes): a
+            // piece may come out empty
+            const SeedSource &S = sources[si];
+            SrcTabs &T = *stabs[si];
+            const uint64_t *nbg = S.new_bg ? T.new_bg.p : nullptr;
+            unsigned long long *n_out = S.drops ? counters.p + 2 : nullptr;
             const double tb0 = now_ms();
             const int64_t piece = piece_seeds > 0 ? std::min<int64_t>(piece_seeds, (int64_t)cap) : (int64_t)cap;
+            int64_t kept_seeds = 0;
             for (int flat = 0; flat < 2; flat++) {
-                const int64_t total = flat ? base_out : base_main;
+                const int64_t total = flat ? T.n_out : T.n_main;
                 for (int64_t s0 = 0; s0 < total; s0 += piece) {
-                    const int64_t n = std::min<int64_t>(piece, total - s0);
+                    int64_t n = std::min<int64_t>(piece, total - s0);
                     const double td0 = dbg ? (bsync(ix), now_ms()) : 0;
-                    sp_dump_range(base, ix->st, flat ? base_out_off : base_md_off, flat != 0, s0, s0 + n, s_mask.p, s_kmer.p, s_val.p);
+                    if (n_out) HIPCHK(hipMemsetAsync(n_out, 0, sizeof(unsigned long long), ix->st));
+                    sp_dump_range(S.ix, ix->st, flat ? T.out_off : T.md_off, flat != 0, s0, s0 + n, s_mask.p, s_kmer.p, s_val.p, nbg, n_out);
+                    if (n_out) {
+                        unsigned long long got = 0;
+                        HIPCHK(hipMemcpyAsync(&got, n_out, sizeof got, hipMemcpyDeviceToHost, ix->st));
+                        bsync(ix);
+                        if (got > (unsigned long long)n) throw HipError("index build: a compacted decode piece holds more seeds than were decoded");
+                        n = (int64_t)got;
+                    }
                     if (dbg) {
                         bsync(ix);
                         t_dump += now_ms() - td0;
                     }
+                    kept_seeds += n;
                     if (pass == 0) packer.count(s_mask.p, s_kmer.p, s_val.p, n);
                     else packer.place(s_mask.p, s_kmer.p, s_val.p, n);
                 }
@@ -1038,8 +1090,9 @@ static void build_seed_index(lm_index *ix, const std::vector<int32_t> &pfx, cons
             bsync(ix);
             t_base += now_ms() - tb0;
             if (dbg)
-                fprintf(stderr, "[lm] builder pass %d: the base's %lld seeds (%lld outliers) decoded and packed in pieces of %lld: %.1f ms, "
-                                "of which the decode kernel %.1f ms (cumulative)\n", pass, (long long)(base_main + base_out), (long long)base_out,
+                fprintf(stderr, "[lm] builder pass %d: %s's %lld seeds (%lld outliers; %lld kept, %s) decoded and packed in pieces of %lld: %.1f ms, "
+                                "of which the decode kernel %.1f ms (cumulative)\n", pass, S.what, (long long)(T.n_main + T.n_out), (long long)T.n_out,
+                        (long long)kept_seeds, !S.new_bg ? "keys as they are" : S.drops ? "keys rewritten, compacted" : "keys rewritten",
                         (long long)piece, t_base, t_dump);
         }
         for (const Chunk &c : chunks) {
@@ -1143,31 +1196,31 @@ static void builder_finish(lm_index_builder *b) {
     bsync(ix);
     b->slabs.clear();
     const lm_index *base = b->base;
-    const int64_t nbase = b->nbase;
-    if (base) {
-        // the base's records into the slots planned for them in front of the added ones, record by record: an opened index
-        // packs its store more tightly than build_slot_bytes, and a host-resident record comes from its pinned segment.
-        // Device records whose slots lie as far apart here as there (a base built by this builder) go as one copy.
+    for (const lm_index_builder::Source &S : b->sources) {
+        // a source's records into the slots planned for them, record by record: an opened index packs its store more tightly
+        // than build_slot_bytes, and a host-resident record comes from its pinned segment.  Device records whose slots lie as
+        // far apart here as there (a source built by this builder, taken whole) go as one copy.
+        const lm_index *src = S.ix;
         int64_t run_src = -1, run_dst = 0, run_len = 0;
         auto flush = [&]() {
-            if (run_src >= 0) HIPCHK(hipMemcpyAsync(ix->d_gbits.p + run_dst, base->d_gbits.p + run_src, (size_t)run_len, hipMemcpyDeviceToDevice, ix->st));
+            if (run_src >= 0) HIPCHK(hipMemcpyAsync(ix->d_gbits.p + run_dst, src->d_gbits.p + run_src, (size_t)run_len, hipMemcpyDeviceToDevice, ix->st));
             run_src = -1;
         };
-        for (int64_t l = 0; l < nbase; l++) {
-            const HostGenome &G = h.genomes[(size_t)l];
-            const int64_t nb = ((int64_t)G.len + 3) >> 2, src = base->host.genomes[(size_t)l].bits_off;
-            const uint8_t *hp = base->g_hhost.empty() ? nullptr : base->g_hhost[(size_t)l];
+        for (const auto &sd : S.recs) {
+            const HostGenome &G = h.genomes[(size_t)sd.second];
+            const int64_t nb = ((int64_t)G.len + 3) >> 2, so = src->host.genomes[(size_t)sd.first].bits_off;
+            const uint8_t *hp = src->g_hhost.empty() ? nullptr : src->g_hhost[(size_t)sd.first];
             if (hp) {
                 flush();
                 HIPCHK(hipMemcpyAsync(ix->d_gbits.p + G.bits_off, hp, (size_t)nb, hipMemcpyHostToDevice, ix->st));
                 continue;
             }
-            if (run_src >= 0 && src - run_src == G.bits_off - run_dst && src >= run_src + run_len) {
-                run_len = src - run_src + nb;
+            if (run_src >= 0 && so - run_src == G.bits_off - run_dst && so >= run_src + run_len) {
+                run_len = so - run_src + nb;
                 continue;
             }
             flush();
-            run_src = src;
+            run_src = so;
             run_dst = G.bits_off;
             run_len = nb;
         }
@@ -1192,7 +1245,14 @@ static void builder_finish(lm_index_builder *b) {
     if (h.shard_count > 1) h.g2local = b->g2local;
     // chunks of records: as many as the per-record scratch (16 B per mask) allows in 128 MB, and at most 2^30 bases
     const int64_t ch_records = std::min<int64_t>(2048, ((int64_t)128 << 20) / ((int64_t)h.M * 16));
-    build_seed_index(ix, b->pfx, b->reg_off, b->reg_s, b->reg_e, bo.max_desert, bo.seed_dist, ch_records, (int64_t)1 << 30, base, nbase, b->rq);
+    std::vector<SeedSource> sources;
+    std::vector<std::string> names;
+    for (size_t i = 0; i < b->sources.size(); i++) names.push_back(b->sources[i].ix == base ? std::string("the base") : "source " + std::to_string(i));
+    for (size_t i = 0; i < b->sources.size(); i++) {
+        const lm_index_builder::Source &S = b->sources[i];
+        sources.push_back(SeedSource{S.ix, S.new_bg.empty() ? nullptr : &S.new_bg, S.drops, names[i].c_str()});
+    }
+    build_seed_index(ix, b->pfx, b->reg_off, b->reg_s, b->reg_e, bo.max_desert, bo.seed_dist, ch_records, (int64_t)1 << 30, sources, b->borrowed, b->rq);
 }
 
 } // namespace lm
@@ -1254,11 +1314,14 @@ lm_status lm_index_builder_new(const lm_build_opt *bo, const lm_options *opt, co
 // in any order: so the base's seeds are decoded from its image (k_sp_dump_range), the added records are captured, and finish()
 // packs both into the image one build of all the genomes would have given.  Here: the settings, the check that the base's
 // batches can be continued, and the base's host tables copied in front of what add() appends.
-lm_status lm_index_builder_extend(lm_index *base, const lm_build_opt *bo_in, const lm_residency *res, lm_index_builder **out) {
+// lm_index_builder_like shares all of it but the base: the masks, options, device and build settings of `model`, no record.
+static lm_status builder_from_model(const char *who, lm_index *base, bool continued, const lm_build_opt *bo_in, const lm_residency *res,
+                                    lm_index_builder **out) {
     if (!out) return LM_ERR_ARG;
     *out = nullptr;
+    const std::string w(who);
     if (!base) {
-        g_open_error = "lm_index_builder_extend: an index to continue is needed";
+        g_open_error = w + (continued ? ": an index to continue is needed" : ": an index to take the settings from is needed");
         return LM_ERR_ARG;
     }
     lm_res_request rq;
@@ -1277,7 +1340,7 @@ lm_status lm_index_builder_extend(lm_index *base, const lm_build_opt *bo_in, con
                             : bo_in->genome_batch_size != bh.genome_batch_size ? "genome_batch_size"
                                                                                : nullptr;
         if (field) {
-            g_open_error = std::string("lm_index_builder_extend: ") + field + " of the build options differs from the index that is continued";
+            g_open_error = w + ": " + field + " of the build options differs from the index that is " + (continued ? "continued" : "the model");
             return LM_ERR_ARG;
         }
         bo = *bo_in;
@@ -1290,38 +1353,42 @@ lm_status lm_index_builder_extend(lm_index *base, const lm_build_opt *bo_in, con
     bo.mask_seed = bh.rand_seed; // (the masks are the base's, whatever seed made them)
     bo.contig_interval = bh.contig_interval;
     bo.genome_batch_size = bh.genome_batch_size;
-    if (!build_opt_ok("lm_index_builder_extend", bo, g_open_error)) return LM_ERR_ARG;
-    if (bh.synthetic && bh.shard_count > 1) {
-        g_open_error = "lm_index_builder_extend: a shard of a synthetic set cannot be continued (its records are numbered without a table)";
-        return LM_ERR_ARG;
-    }
-    // record n lies in batch n / genome_batch_size: every batch of the base but the last must be full
-    const int nb = bh.genome_batches;
-    bool regular = nb >= 1 && (int)bh.batch_first.size() == nb + 1 && bh.batch_first[0] == 0;
-    for (int i = 0; regular && i < nb; i++) {
-        const int64_t n = bh.batch_first[(size_t)i + 1] - bh.batch_first[(size_t)i];
-        regular = i + 1 < nb ? n == bo.genome_batch_size : (n >= 1 && n <= bo.genome_batch_size);
-    }
-    if (!regular) {
-        g_open_error = "lm_index_builder_extend: the genome batches of the index are irregular (not every batch but the last holds genome_batch_size = " +
-                       std::to_string(bo.genome_batch_size) + " records, as in an index of the reference with split genomes): its records cannot be numbered on";
-        return LM_ERR_ARG;
-    }
-    const int64_t base_records = bh.batch_first[(size_t)nb];
-    const int64_t nbase = (int64_t)bh.genomes.size();
-    if (bh.shard_count > 1 ? (int64_t)bh.g2local.size() != base_records : nbase != base_records) {
-        g_open_error = "lm_index_builder_extend: the record tables of the index do not agree with its batches";
-        return LM_ERR_ARG;
+    if (!build_opt_ok(who, bo, g_open_error)) return LM_ERR_ARG;
+    int64_t base_records = 0, nbase = 0;
+    if (continued) {
+        if (bh.synthetic && bh.shard_count > 1) {
+            g_open_error = w + ": a shard of a synthetic set cannot be continued (its records are numbered without a table)";
+            return LM_ERR_ARG;
+        }
+        // record n lies in batch n / genome_batch_size: every batch of the base but the last must be full
+        const int nb = bh.genome_batches;
+        bool regular = nb >= 1 && (int)bh.batch_first.size() == nb + 1 && bh.batch_first[0] == 0;
+        for (int i = 0; regular && i < nb; i++) {
+            const int64_t n = bh.batch_first[(size_t)i + 1] - bh.batch_first[(size_t)i];
+            regular = i + 1 < nb ? n == bo.genome_batch_size : (n >= 1 && n <= bo.genome_batch_size);
+        }
+        if (!regular) {
+            g_open_error = w + ": the genome batches of the index are irregular (not every batch but the last holds genome_batch_size = " +
+                           std::to_string(bo.genome_batch_size) + " records, as in an index of the reference with split genomes): its records cannot be numbered on";
+            return LM_ERR_ARG;
+        }
+        base_records = bh.batch_first[(size_t)nb];
+        nbase = (int64_t)bh.genomes.size();
+        if (bh.shard_count > 1 ? (int64_t)bh.g2local.size() != base_records : nbase != base_records) {
+            g_open_error = w + ": the record tables of the index do not agree with its batches";
+            return LM_ERR_ARG;
+        }
     }
     std::unique_ptr<lm_index_builder> b(new lm_index_builder());
     b->bo = bo;
     b->rq = rq;
-    b->base = base;
-    b->nbase = nbase;
-    b->base_records = base_records;
-    b->nrecords = base_records;
-    b->ninput = bh.input_genomes > 0 ? bh.input_genomes : base_records;
-    b->input_bases = bh.total_bases;
+    if (continued) {
+        b->base = base;
+        b->base_records = base_records;
+        b->nrecords = base_records;
+        b->ninput = bh.input_genomes > 0 ? bh.input_genomes : base_records;
+        b->input_bases = bh.total_bases;
+    }
     if (const char *e = getenv("LM_BUILD_SLAB_KB")) b->slab_bytes = std::max<int64_t>(64, atoll(e)) << 10;
     try {
         lm_index *ix = new lm_index();
@@ -1334,25 +1401,114 @@ lm_status lm_index_builder_extend(lm_index *base, const lm_build_opt *bo_in, con
         h.rand_seed = bh.rand_seed;
         h.max_seed_dist = bh.max_seed_dist;
         h.seed_dist_in_desert = bh.seed_dist_in_desert;
-        // the base's tables in front: add() appends to them as it does in a fresh builder
-        h.genomes = bh.genomes;
-        h.others = bh.others;
-        h.other_of = bh.other_of;
-        h.chunk_of = bh.chunk_of;
-        for (const auto &kv : bh.chunk_of) b->nlists = std::max(b->nlists, kv.second.list + 1);
-        if (h.shard_count > 1) b->g2local = bh.g2local;
-        b->reg_off.assign((size_t)nbase + 1, 0); // (no skip regions are needed for records that are not captured again)
-        for (int64_t l = 0; l < nbase; l++) {
-            HostGenome &G = h.genomes[(size_t)l];
-            G.bits_off = b->store_bytes; // its slot in the new store, filled by finish()
-            b->store_bytes += build_slot_bytes(G.len);
-            b->max_len = std::max<int64_t>(b->max_len, G.len);
+        if (continued) {
+            // the base's tables in front: add() appends to them as it does in a fresh builder
+            h.genomes = bh.genomes;
+            h.others = bh.others;
+            h.other_of = bh.other_of;
+            h.chunk_of = bh.chunk_of;
+            for (const auto &kv : bh.chunk_of) b->nlists = std::max(b->nlists, kv.second.list + 1);
+            if (h.shard_count > 1) b->g2local = bh.g2local;
+            b->reg_off.assign((size_t)nbase + 1, 0); // (no skip regions are needed for records that are not captured again)
+            b->borrowed.assign((size_t)nbase, 1);
+            lm_index_builder::Source S;
+            S.ix = base; // (its records keep their keys: no rewrite table)
+            for (int64_t l = 0; l < nbase; l++) {
+                HostGenome &G = h.genomes[(size_t)l];
+                G.bits_off = b->store_bytes; // its slot in the new store, filled by finish()
+                b->store_bytes += build_slot_bytes(G.len);
+                b->max_len = std::max<int64_t>(b->max_len, G.len);
+                S.recs.emplace_back(l, l);
+            }
+            b->sources.push_back(std::move(S));
         }
     } catch (const std::exception &e) {
         g_open_error = e.what();
         return LM_ERR_HIP;
     }
     *out = b.release();
+    return LM_OK;
+}
+lm_status lm_index_builder_extend(lm_index *base, const lm_build_opt *bo, const lm_residency *res, lm_index_builder **out) {
+    return builder_from_model("lm_index_builder_extend", base, true, bo, res, out);
+}
+lm_status lm_index_builder_like(const lm_index *model, const lm_build_opt *bo, const lm_residency *res, lm_index_builder **out) {
+    return builder_from_model("lm_index_builder_like", const_cast<lm_index *>(model), false, bo, res, out); // (its lock is taken; nothing of it is written)
+}
+
+// The records of a resident index appended to the builder ("Joining and subsetting resident indexes"): the
+// checks, the plan (lm_join_plan.h) and copies of the source's host tables under the new keys.  No device work happens here;
+// finish() copies the 2-bit records and decodes the seeds.
+lm_status lm_index_builder_add_index(lm_index_builder *b, lm_index *src, const uint64_t *keep, size_t nkeep) {
+    if (!b) return LM_ERR_ARG;
+    if (b->broken) {
+        b->err = "lm_index_builder_add_index: an earlier device error left this builder unusable: " + b->err;
+        return LM_ERR_HIP;
+    }
+    auto refuse = [&](const std::string &why) {
+        b->err = "lm_index_builder_add_index: " + why;
+        return LM_ERR_ARG;
+    };
+    if (!src) return refuse("a source index is needed");
+    lm_index *ix = b->ix;
+    HostIndex &h = ix->host;
+    if (src == b->base) return refuse("the source is the index this builder continues: its records are there already");
+    for (const auto &S : b->sources)
+        if (S.ix == src) return refuse("this source was added to the builder before");
+    if (h.shard_count > 1) return refuse("the builder is sharded (shard_count = " + std::to_string(h.shard_count) + "): joining shards is not supported");
+    std::lock_guard<std::mutex> src_lock(src->mu);
+    const HostIndex &sh = src->host;
+    if (sh.shard_count > 1) return refuse("the source is shard " + std::to_string(sh.shard_rank) + " of " + std::to_string(sh.shard_count) + ": joining shards is not supported");
+    if (src->device != ix->device) return refuse("the source is on device " + std::to_string(src->device) + ", the builder on device " + std::to_string(ix->device));
+    if (sh.k != h.k) return refuse("k differs: the source has " + std::to_string(sh.k) + ", the builder " + std::to_string(h.k));
+    if (sh.contig_interval != h.contig_interval)
+        return refuse("contig_interval differs: the source has " + std::to_string(sh.contig_interval) + ", the builder " + std::to_string(h.contig_interval));
+    if (sh.M != h.M) return refuse("the number of masks differs: the source has " + std::to_string(sh.M) + ", the builder " + std::to_string(h.M));
+    for (int i = 0; i < h.M; i++)
+        if (sh.masks[(size_t)i] != h.masks[(size_t)i])
+            return refuse("the mask values differ (first at mask " + std::to_string(i) + "): the two mask sets were not made from the same seed");
+    if ((int64_t)sh.genomes.size() != src->view.ngenomes || src->view.shard_count > 1 || src->view.g2local)
+        return refuse("the record tables of the source do not agree with its image");
+    std::vector<JoinSrcRecord> table(sh.genomes.size());
+    for (size_t l = 0; l < sh.genomes.size(); l++) {
+        table[l].key = sh.genomes[l].bg;
+        const auto it = sh.chunk_of.find(sh.genomes[l].bg);
+        if (it != sh.chunk_of.end() && it->second.n > 1) {
+            table[l].list = it->second.list;
+            table[l].list_n = it->second.n;
+            table[l].list_idx = it->second.idx;
+        }
+    }
+    JoinPlan plan;
+    std::string why;
+    if (plan_join(table, keep, nkeep, b->nrecords, b->bo.genome_batch_size, b->nlists, plan, why) != JOIN_OK) return refuse(why);
+    for (const JoinKept &k : plan.kept)
+        if (sh.genomes[(size_t)k.src_local].len >= (1 << 28)) return refuse("a record of the source has 2^28 bases or more");
+    // (the captured records so far lie in slabs that are consecutive pieces of the store: the slots of the borrowed records
+    // come behind them, so the next captured record opens a new slab)
+    if (!b->slabs.empty()) b->slabs.back()->cap = b->slabs.back()->used;
+    lm_index_builder::Source S;
+    S.ix = src;
+    S.drops = plan.drops;
+    for (const JoinKept &k : plan.kept) {
+        HostGenome G = sh.genomes[(size_t)k.src_local]; // id, contig ids and sizes, genome_size, len, nseqs
+        G.bg = k.key;
+        G.global = k.number;
+        G.bits_off = b->store_bytes; // its slot in the new store, filled by finish()
+        b->store_bytes += build_slot_bytes(G.len);
+        b->max_len = std::max<int64_t>(b->max_len, G.len);
+        b->input_bases += G.genome_size;
+        if (k.list >= 0) h.chunk_of[k.key] = HostIndex::ChunkInfo{k.list, k.list_n, k.list_idx};
+        S.recs.emplace_back(k.src_local, (int64_t)h.genomes.size());
+        b->reg_off.push_back((int32_t)b->reg_s.size()); // (no skip regions: the record is not captured)
+        b->borrowed.push_back(1);
+        h.genomes.push_back(std::move(G));
+    }
+    S.new_bg = std::move(plan.new_bg);
+    b->sources.push_back(std::move(S));
+    b->nrecords += (int64_t)plan.kept.size();
+    b->ninput += plan.ninput;
+    b->nlists = plan.nlists;
     return LM_OK;
 }
 
@@ -1439,6 +1595,7 @@ lm_status lm_index_builder_add(lm_index_builder *b, const char *genome_id, const
             }
             b->reg_off.push_back((int32_t)b->reg_s.size());
             b->max_len = std::max<int64_t>(b->max_len, R.len);
+            b->borrowed.push_back(0);
             h.genomes.push_back(std::move(G));
         } else {
             G.bits_off = -1;
@@ -1465,15 +1622,23 @@ lm_status lm_index_builder_finish(lm_index_builder *bp, lm_index **out) {
         g_open_error = b->nrecords == b->base_records ? "lm_index_builder_finish: no genome was added" : "lm_index_builder_finish: no genome of this shard was added";
         return LM_ERR_ARG;
     }
-    // (an extending builder reads the base's image and store: no search or save of the base runs meanwhile)
-    std::unique_lock<std::mutex> base_lock;
-    if (b->base) base_lock = std::unique_lock<std::mutex>(b->base->mu);
+    // (the builder reads the images and stores of the base and of every source: no search or save of them runs meanwhile.  The
+    // locks are taken in the order of the handles' addresses, so that two finishes that share sources cannot wait for each other)
+    std::vector<lm_index *> held;
+    for (const auto &S : b->sources) held.push_back(S.ix);
+    std::sort(held.begin(), held.end(), std::less<lm_index *>());
+    held.erase(std::unique(held.begin(), held.end()), held.end());
+    std::vector<std::unique_lock<std::mutex>> src_locks;
+    for (lm_index *p : held) src_locks.emplace_back(p->mu);
     try {
         HIPCHK(hipSetDevice(b->ix->device));
         builder_finish(b.get());
     } catch (const DeviceOOM &e) {
         g_open_error = e.what();
-        if (b->base)
+        if (b->sources.size() > (b->base ? 1u : 0u))
+            g_open_error = "lm_index_builder_finish: the images and stores of the " + std::to_string(b->sources.size()) + " resident indexes that are read" +
+                           ", the new store, the new image and the seed staging do not fit the device together (the sources are intact): " + g_open_error;
+        else if (b->base)
             g_open_error = "lm_index_builder_finish: the base's image, the extended image and the seed staging do not fit the device together (the base is "
                            "intact): " + g_open_error;
         return LM_ERR_NOMEM;
@@ -1574,7 +1739,7 @@ lm_status lm_index_build_synthetic_ex(const lm_synth_spec *spec, const lm_option
             G.bits_off = l * sp.gbytes;
         }
         const std::vector<int32_t> no_regions((size_t)nlocal + 1, 0);
-        build_seed_index(ix, pfx, no_regions, {}, {}, spec->max_desert, spec->seed_dist, 2048, INT64_MAX, nullptr, 0, rq);
+        build_seed_index(ix, pfx, no_regions, {}, {}, spec->max_desert, spec->seed_dist, 2048, INT64_MAX, {}, {}, rq);
     } catch (const PinnedOOM &e) {
         g_open_error = e.what();
         delete ix;

@@ -424,8 +424,12 @@ struct SeedPacker {
 // The seeds [s0, s1) of a resident image decoded on stream `st` into the arrays count() / place() take (k_sp_dump_range):
 // main seeds as md_off numbers them, or (flat) outliers as out_off does; `off` is the host's copy of that table, [2M + 1].
 // The caller keeps `src` from changing (its mutex) and the arrays at least s1 - s0 long.
+// new_bg (device, [src's local records], lm_join_plan.h) null: the values carry src's own genome keys.  Otherwise they carry
+// new_bg[record]; with n_out (a zeroed device counter) the seeds of JOIN_DROP records are left out, the rest lie compacted
+// at [0, *n_out) in no particular order; without it no entry of the table may be JOIN_DROP.
 void sp_dump_range(const lm_index *src, hipStream_t st, const std::vector<int64_t> &off, bool flat, int64_t s0, int64_t s1,
-                   uint16_t *s_mask, uint64_t *s_kmer, uint64_t *s_val);
+                   uint16_t *s_mask, uint64_t *s_kmer, uint64_t *s_val, const uint64_t *new_bg = nullptr,
+                   unsigned long long *n_out = nullptr);
 } // namespace lm
 
 // Experiment / A-B switches of the kernels, read from the environment ONCE when the handle is created (a search never calls

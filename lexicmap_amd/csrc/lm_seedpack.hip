@@ -296,10 +296,23 @@ __global__ void k_sp_dump_list(DevIndexView ix, uint32_t md, int64_t n_main, uin
 // blockDim.x seeds finds its first and last list and the partitions of its first and last seed once (uniform searches:
 // scalar loads); a lane searches between those brackets only (lm_seed_walk.h), which is a handful of partitions wherever
 // lists are longer than a tile.  The outlier lists are flat pairs: a copy with the mask id beside it.
-template <bool FLAT>
+// MODE says what genome key a value carries (lm_index_builder_add_index, lm_join_plan.h):
+//   SP_DUMP_KEEP     the source's own key (new_bg unused): lm_index_builder_extend's base
+//   SP_DUMP_REWRITE  new_bg[local record]; no entry of the table is JOIN_DROP.  Same access pattern, nothing else
+//   SP_DUMP_COMPACT  new_bg[local record], and a seed whose record is JOIN_DROP is not written: every wavefront ballots
+//                    "kept", its first lane reserves popcount slots of the output with ONE atomic on *n_out (zeroed by the
+//                    host per piece) and the lanes write at that base + their rank among the kept lanes - a wavefront's
+//                    three output streams stay contiguous, the order of the wavefronts in the output is whatever the
+//                    atomics give (the packer's image does not depend on it).  At most s1 - s0 seeds are written.
+// An outlier's value is in the reference's layout already: its record is found from the source's key through batch_first
+// (sources are unsharded: lm_index_builder_add_index); a key outside the source's records (no index holds one) is dropped
+// under COMPACT and never used as an index into the table.
+enum { SP_DUMP_KEEP = 0, SP_DUMP_REWRITE = 1, SP_DUMP_COMPACT = 2 };
+template <bool FLAT, int MODE>
 __global__ __launch_bounds__(256) void k_sp_dump_range(DevIndexView ix, int64_t l0, int64_t l1, int64_t s0, int64_t s1,
                                                         uint16_t *__restrict__ s_mask, uint64_t *__restrict__ s_kmer,
-                                                        uint64_t *__restrict__ s_val) {
+                                                        uint64_t *__restrict__ s_val, const uint64_t *__restrict__ new_bg,
+                                                        unsigned long long *__restrict__ n_out) {
     const int64_t *__restrict__ off = FLAT ? ix.out_off : ix.md_off;
     const int P = ix.P1 - 1;
     const int val_bits = ix.gid_bits + ix.pos_bits + 1;
@@ -313,36 +326,84 @@ __global__ __launch_bounds__(256) void k_sp_dump_range(DevIndexView ix, int64_t 
             pl = (int)sw_last_le(ix.part_tab + ll * ix.P1, lf == ll ? pf : 0, P - 1, t1 - off[ll]);
         }
         const int64_t i = t0 + threadIdx.x;
-        if (i > t1) continue;
-        const int64_t md = sw_last_le(off, lf, ll, i), o = i - s0;
-        s_mask[o] = (uint16_t)(md >> 1);
-        if (FLAT) {
-            s_kmer[o] = ix.out_kmers[i];
-            s_val[o] = ix.out_vals[i];
-        } else {
-            const int part = sw_partition(ix.part_tab + md * ix.P1, P, i - off[md], md == lf, pf, md == ll, pl);
-            const uint64_t pfx = ix.masks[md >> 1] >> ((ix.K - ix.mask_prefix) << 1);
-            const uint64_t rem = lm_bits_get(ix.pk_keys, i, ix.key_bits);
-            const uint64_t pv = lm_bits_get(ix.pk_vals, i, val_bits);
-            s_kmer[o] = (((pfx << (ix.part_bases << 1)) | (uint64_t)part) << ix.key_bits) | rem;
-            s_val[o] = lm_unpack_seed_val(pv, ix.g_bg[lm_packed_val_genome(pv, ix.pos_bits)], ix.pos_bits, (int)(md & 1));
+        if (MODE != SP_DUMP_COMPACT && i > t1) continue; // (COMPACT: every lane of the wavefront takes part in the ballot below)
+        bool kept = i <= t1;
+        int64_t md = 0;
+        uint64_t kmer = 0, val = 0;
+        if (kept) {
+            md = sw_last_le(off, lf, ll, i);
+            if (FLAT) {
+                kmer = ix.out_kmers[i];
+                val = ix.out_vals[i];
+                if (MODE != SP_DUMP_KEEP) {
+                    const uint64_t bg = val >> 30, batch = bg >> 17;
+                    const int64_t local = batch < (uint64_t)ix.nbatches ? ix.batch_first[batch] + (int64_t)(bg & 0x1ffff) : -1;
+                    if (local >= 0 && local < ix.ngenomes) {
+                        const uint64_t nb = new_bg[local];
+                        if (MODE == SP_DUMP_COMPACT && nb == ~0ull) kept = false;
+                        val = (nb << 30) | (val & 0x3fffffffull);
+                    } else if (MODE == SP_DUMP_COMPACT) {
+                        kept = false;
+                    }
+                }
+            } else {
+                const int part = sw_partition(ix.part_tab + md * ix.P1, P, i - off[md], md == lf, pf, md == ll, pl);
+                const uint64_t pfx = ix.masks[md >> 1] >> ((ix.K - ix.mask_prefix) << 1);
+                const uint64_t rem = lm_bits_get(ix.pk_keys, i, ix.key_bits);
+                const uint64_t pv = lm_bits_get(ix.pk_vals, i, val_bits);
+                kmer = (((pfx << (ix.part_bases << 1)) | (uint64_t)part) << ix.key_bits) | rem;
+                const uint64_t local = lm_packed_val_genome(pv, ix.pos_bits);
+                uint64_t bg;
+                if (MODE == SP_DUMP_KEEP) {
+                    bg = ix.g_bg[local];
+                } else { // (a value past the source's records - no image holds one - reads nothing outside the table)
+                    bg = (int64_t)local < ix.ngenomes ? new_bg[local] : ~0ull;
+                    if (MODE == SP_DUMP_COMPACT && bg == ~0ull) kept = false;
+                }
+                val = lm_unpack_seed_val(pv, bg, ix.pos_bits, (int)(md & 1));
+            }
+        }
+        int64_t o = i - s0;
+        if (MODE == SP_DUMP_COMPACT) {
+            const unsigned long long bal = __ballot(kept);
+            const int lane = (int)(threadIdx.x & 63u);
+            unsigned long long base = 0;
+            if (lane == 0 && bal) base = atomicAdd(n_out, (unsigned long long)__popcll(bal));
+            base = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(base >> 32)) << 32) |
+                   (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+            o = (int64_t)base + __popcll(bal & ((1ull << lane) - 1ull));
+        }
+        if (kept && (MODE != SP_DUMP_COMPACT || o < s1 - s0)) {
+            s_mask[o] = (uint16_t)(md >> 1);
+            s_kmer[o] = kmer;
+            s_val[o] = val;
         }
     }
 }
 
 void sp_dump_range(const lm_index *src, hipStream_t st, const std::vector<int64_t> &off, bool flat, int64_t s0, int64_t s1,
-                   uint16_t *s_mask, uint64_t *s_kmer, uint64_t *s_val) {
+                   uint16_t *s_mask, uint64_t *s_kmer, uint64_t *s_val, const uint64_t *new_bg, unsigned long long *n_out) {
     if (s1 <= s0) return;
     const int64_t nmd = (int64_t)off.size() - 1;
     if (s0 < 0 || s1 > off[(size_t)nmd]) throw HipError("seed image: a decode piece outside the image");
+    if (n_out && !new_bg) throw HipError("seed image: a compacting decode needs a rewrite table");
     int64_t l0, l1;
     sw_piece_lists(off.data(), nmd, s0, s1, &l0, &l1);
     // (a bandwidth kernel: at most 8 workgroups per CU, the rest of the piece by grid stride)
     const unsigned grid = (unsigned)std::min<int64_t>((s1 - s0 + 255) / 256, 2048);
-    if (flat)
-        hipLaunchKernelGGL(k_sp_dump_range<true>, dim3(grid), dim3(256), 0, st, src->view, l0, l1, s0, s1, s_mask, s_kmer, s_val);
-    else
-        hipLaunchKernelGGL(k_sp_dump_range<false>, dim3(grid), dim3(256), 0, st, src->view, l0, l1, s0, s1, s_mask, s_kmer, s_val);
+    const int mode = !new_bg ? SP_DUMP_KEEP : n_out ? SP_DUMP_COMPACT : SP_DUMP_REWRITE;
+#define SP_DUMP_LAUNCH(F, M)                                                                                                        \
+    hipLaunchKernelGGL((k_sp_dump_range<F, M>), dim3(grid), dim3(256), 0, st, src->view, l0, l1, s0, s1, s_mask, s_kmer, s_val, new_bg, n_out)
+    if (flat) {
+        if (mode == SP_DUMP_KEEP) SP_DUMP_LAUNCH(true, SP_DUMP_KEEP);
+        else if (mode == SP_DUMP_REWRITE) SP_DUMP_LAUNCH(true, SP_DUMP_REWRITE);
+        else SP_DUMP_LAUNCH(true, SP_DUMP_COMPACT);
+    } else {
+        if (mode == SP_DUMP_KEEP) SP_DUMP_LAUNCH(false, SP_DUMP_KEEP);
+        else if (mode == SP_DUMP_REWRITE) SP_DUMP_LAUNCH(false, SP_DUMP_REWRITE);
+        else SP_DUMP_LAUNCH(false, SP_DUMP_COMPACT);
+    }
+#undef SP_DUMP_LAUNCH
     HIPCHK(hipGetLastError());
 }
 
