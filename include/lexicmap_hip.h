@@ -240,6 +240,64 @@ const uint64_t *lm_index_masks(const lm_index *idx);
  * (kv/kv-reader.go:762), what `lexicmap utils kmers --mask` prints (kmers.go:101-180). Call with cap = 0 (or both arrays
  * NULL) for the count; 0 < cap < count returns LM_ERR_ARG with *n = count and writes nothing. */
 lm_status lm_index_mask_seeds(lm_index *idx, int32_t mask, uint64_t *kmers, uint64_t *vals, size_t cap, size_t *n);
+/* Where the seeds of genome records are, from the resident image: what `lexicmap utils seed-pos` reads from
+ * seed_positions.bin (seed-pos.go), a file a resident index does not have.  One device pass over the packed values of the
+ * forward lists (the reversed lists repeat the same positions), one radix sort, one segmentation; the genome bytes are not
+ * read, so it works wherever they live, on built, opened, extended, joined and subset handles.
+ *   keys[0..nkeys): record keys (batch << 17 | index); keys == NULL with nkeys == 0: every record of this handle in record
+ *     order; keys != NULL with nkeys == 0: no record, an empty result.  Record slot s of the result is keys[s] (or the
+ *     handle's s-th record).
+ *   lm_seedpos_get: returns the number of record slots n; keys[n], off[n + 1], locs[off[n]]: the position list of slot s is
+ *     locs[off[s] .. off[s + 1]), loc = pos << 1 | strand (the reference's value without genome key and reverse bit:
+ *     (value >> 1) & (2^29 - 1)), ascending as uint32; a position captured by two masks is there twice
+ *     (lib-index-build.go:1066-1072, 1409-1417).  Any of the three pointers may be NULL.  Valid until lm_seedpos_free.
+ * LM_ERR_ARG, text in lm_last_error(idx), handle still usable: a key that is no record of this handle (a sharded handle
+ * answers for its own records: the text says when the key is a record of another shard), a key given twice, keys == NULL
+ * with nkeys > 0.  LM_ERR_NOMEM (text says what had to fit) when the 20 B per selected forward seed - two 8-byte arrays of
+ * sort keys and the 4-byte position list - or the radix sort's scratch do not fit beside the index. */
+typedef struct lm_seedpos lm_seedpos;
+lm_status lm_index_seed_positions(lm_index *idx, const uint64_t *keys, size_t nkeys, lm_seedpos **out);
+size_t lm_seedpos_get(const lm_seedpos *sp, const uint64_t **keys, const int64_t **off, const uint32_t **locs);
+void lm_seedpos_free(lm_seedpos *sp);
+/* The distances between consecutive seeds of the selected records, computed on the device from the sorted position lists
+ * (the rule: lexicmap_amd/csrc/lm_seed_dist.h; seed-pos.go:385-457 without its flag bit).  A record's
+ * contigs start at s_0 = 0, s_{c+1} = s_c + len_c + contig_interval; position p = loc >> 1 belongs to the last contig with
+ * s_c <= p; the first position of a contig has dist = p - s_c, every other dist = p - the position before; a contig without
+ * seeds contributes nothing; a run of N inside a contig counts as sequence.  A position is REPORTED when dist >= min_dist.
+ *   records: one per slot, whatever min_dist is - seeds (entries of the position list), the largest dist and the first
+ *     position that has it (both 0 without seeds), contigs and how many of them hold no seed.
+ *   hist: hist_bins counters of width hist_width over the reported positions of all selected records (what seed-pos plots),
+ *     the last counter taking everything beyond; hist_bins == 0: none.  At most 4096 counters.
+ *   rows: the reported positions, records in selection order, positions ascending within a record: what
+ *     `utils seed-pos -D min_dist` prints (pos and pos_in_contig are 0-based here, the tool prints them + 1).
+ * opt == NULL: {0, 0, 0}.  LM_ERR_ARG beyond the cases of lm_index_seed_positions: hist_bins > 0 with hist_width < 1,
+ * hist_bins > 4096.  The accessors return the element count; results are valid until lm_seed_dist_free. */
+typedef struct lm_seed_dist_opt {
+    uint32_t min_dist;   /* -D/--min-dist of seed-pos */
+    uint32_t hist_bins;
+    uint32_t hist_width;
+    uint32_t pad;
+} lm_seed_dist_opt;
+typedef struct lm_seed_dist_rec {
+    uint64_t key;
+    int64_t seeds;
+    uint32_t max_dist, max_dist_pos;
+    int32_t contigs, contigs_without_seeds;
+} lm_seed_dist_rec;
+typedef struct lm_seed_dist_row {
+    uint32_t record;         /* slot in the selection */
+    uint32_t contig;         /* index of the contig in the record */
+    uint32_t pos;            /* 0-based in the record's concatenation */
+    uint32_t pos_in_contig;  /* pos - s_c */
+    uint32_t strand;         /* 1: the k-mer was captured on the reverse strand */
+    uint32_t dist;
+} lm_seed_dist_row;
+typedef struct lm_seed_dist lm_seed_dist;
+lm_status lm_index_seed_distances(lm_index *idx, const uint64_t *keys, size_t nkeys, const lm_seed_dist_opt *opt, lm_seed_dist **out);
+size_t lm_seed_dist_records(const lm_seed_dist *sd, const lm_seed_dist_rec **recs);
+size_t lm_seed_dist_hist(const lm_seed_dist *sd, const uint64_t **hist);
+size_t lm_seed_dist_rows(const lm_seed_dist *sd, const lm_seed_dist_row **rows);
+void lm_seed_dist_free(lm_seed_dist *sd);
 /* text of the last error on this handle, or of the last failed lm_index_open when idx == NULL */
 const char *lm_last_error(const lm_index *idx);
 

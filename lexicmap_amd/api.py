@@ -123,6 +123,20 @@ class ResidencyInfo(C.Structure):
                 ("genome_bytes_host", C.c_int64), ("stage_bytes", C.c_int64)]
 
 
+class SeedDistOpt(C.Structure):
+    _fields_ = [("min_dist", C.c_uint32), ("hist_bins", C.c_uint32), ("hist_width", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class SeedDistRec(C.Structure):
+    _fields_ = [("key", C.c_uint64), ("seeds", C.c_int64), ("max_dist", C.c_uint32), ("max_dist_pos", C.c_uint32),
+                ("contigs", C.c_int32), ("contigs_without_seeds", C.c_int32)]
+
+
+class SeedDistRow(C.Structure):
+    _fields_ = [("record", C.c_uint32), ("contig", C.c_uint32), ("pos", C.c_uint32), ("pos_in_contig", C.c_uint32),
+                ("strand", C.c_uint32), ("dist", C.c_uint32)]
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char_p), ("launches", C.c_int64), ("total_ms", C.c_double), ("bytes", C.c_int64)]
 
@@ -205,6 +219,21 @@ def lib():
     L.lm_index_set_genome_filter.argtypes = [vp, C.POINTER(C.c_uint64), C.c_size_t]
     L.lm_index_mask_seeds.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_size_t,
                                       C.POINTER(C.c_size_t)]
+    L.lm_index_seed_positions.argtypes = [vp, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(vp)]
+    L.lm_seedpos_get.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.POINTER(C.c_int64)),
+                                 C.POINTER(C.POINTER(C.c_uint32))]
+    L.lm_seedpos_get.restype = C.c_size_t
+    L.lm_seedpos_free.argtypes = [vp]
+    L.lm_seedpos_free.restype = None
+    L.lm_index_seed_distances.argtypes = [vp, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(SeedDistOpt), C.POINTER(vp)]
+    L.lm_seed_dist_records.argtypes = [vp, C.POINTER(C.POINTER(SeedDistRec))]
+    L.lm_seed_dist_records.restype = C.c_size_t
+    L.lm_seed_dist_hist.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint64))]
+    L.lm_seed_dist_hist.restype = C.c_size_t
+    L.lm_seed_dist_rows.argtypes = [vp, C.POINTER(C.POINTER(SeedDistRow))]
+    L.lm_seed_dist_rows.restype = C.c_size_t
+    L.lm_seed_dist_free.argtypes = [vp]
+    L.lm_seed_dist_free.restype = None
     L.lm_index_fetch.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, C.c_char_p]
     L.lm_index_save.argtypes = [vp, C.c_char_p, C.c_int]
     L.lm_profile_enable.argtypes = [vp, C.c_int]
@@ -396,6 +425,67 @@ class Index:
         if st != 0:
             self._err(st)
         return k[:n.value], v[:n.value]
+
+    @staticmethod
+    def _record_keys(keys):
+        if keys is None:
+            return None, 0
+        ks = [int(k) for k in keys]
+        return (C.c_uint64 * max(len(ks), 1))(*ks), len(ks)
+
+    def _seed_err(self, st):
+        if st == 7:
+            raise ValueError(lib().lm_last_error(self.h).decode())
+        self._err(st)
+
+    def seed_positions(self, keys=None):
+        """lm_index_seed_positions: per selected record (keys: record keys batch << 17 | index in any order; None: every
+        record of this handle in record order) the sorted list of its forward seeds as a numpy uint32 array of
+        pos << 1 | strand - extracted, sorted and cut on the GPU.  ValueError for a key that is no record of this handle
+        (another shard's among them) or is given twice; an empty list of keys gives an empty list."""
+        import numpy as np
+        L = lib()
+        arr, n = self._record_keys(keys)
+        sp = C.c_void_p()
+        st = L.lm_index_seed_positions(self.h, arr, n, C.byref(sp))
+        if st != 0:
+            self._seed_err(st)
+        try:
+            off, locs = C.POINTER(C.c_int64)(), C.POINTER(C.c_uint32)()
+            nrec = L.lm_seedpos_get(sp, None, C.byref(off), C.byref(locs))
+            o = np.ctypeslib.as_array(off, shape=(nrec + 1,))
+            a = np.ctypeslib.as_array(locs, shape=(int(o[nrec]),)).copy() if o[nrec] else np.zeros(0, np.uint32)
+            return [a[o[s]:o[s + 1]] for s in range(nrec)]
+        finally:
+            L.lm_seedpos_free(sp)
+
+    def seed_distances(self, keys=None, min_dist=0, bins=0, bin_width=0):
+        """lm_index_seed_distances: the distances between consecutive seeds of the selected records (keys as in
+        seed_positions), computed on the GPU.  -> dict of numpy arrays: `records` (one per selected record: key, seeds,
+        max_dist, max_dist_pos, contigs, contigs_without_seeds), `hist` (bins counters of bin_width over the reported
+        distances, the last one open-ended) and `rows` (record slot, contig, pos, pos_in_contig, strand, dist of every
+        position with dist >= min_dist, in selection and position order: the lines of `lexicmap utils seed-pos -D`).
+        ValueError as seed_positions, and for bins > 0 with bin_width < 1."""
+        import numpy as np
+        L = lib()
+        arr, n = self._record_keys(keys)
+        opt = SeedDistOpt(min_dist, bins, bin_width, 0)
+        sd = C.c_void_p()
+        st = L.lm_index_seed_distances(self.h, arr, n, C.byref(opt), C.byref(sd))
+        if st != 0:
+            self._seed_err(st)
+        try:
+            def take(fn, ctype, dtype):
+                p = C.POINTER(ctype)()
+                k = fn(sd, C.byref(p))
+                if not k:
+                    return np.zeros(0, dtype)
+                return np.frombuffer(C.string_at(p, k * C.sizeof(ctype)), dtype=dtype)
+            return dict(records=take(L.lm_seed_dist_records, SeedDistRec, np.dtype(SeedDistRec)),
+                        hist=take(L.lm_seed_dist_hist, C.c_uint64, np.uint64),
+                        rows=take(L.lm_seed_dist_rows, SeedDistRow, np.dtype(SeedDistRow)))
+        finally:
+            L.lm_seed_dist_free(sd)
 
     def upload(self, seqs):
         arr, keep = _queries(seqs)

@@ -14,6 +14,7 @@
 // finish() -> every partition sorted by key in place (one wavefront per partition, LDS bitonic network; partitions
 // shared words are merged with masked atomics).  No copy of the unpacked seeds ever exists.
 #include "lm_prims.h"
+#include "lm_seed_dist.h"
 #include "lm_seed_walk.h"
 
 #include <errno.h>
@@ -650,6 +651,501 @@ extern "C" lm_status lm_index_mask_seeds(lm_index *ix, int32_t mask, uint64_t *k
         return LM_ERR_HIP;
     }
 }
+
+// ---- seed positions and seed distances of genome records --------------------------------------------------
+// lm_index_seed_positions / lm_index_seed_distances: the forward seeds of the selected records leave the image as
+// slot << 32 | loc (k_sp_seed_locs), one 64-bit radix sort puts them in selection and position order, k_sp_seed_segment
+// cuts them into the per-record lists, k_sd_pass applies the distance rule of lm_seed_dist.h.
+namespace lm {
+
+struct SeedArg : std::runtime_error { // a refused argument: LM_ERR_ARG, the handle stays usable
+    explicit SeedArg(const std::string &m) : std::runtime_error(m) {}
+};
+
+// which records are wanted: main seeds carry a local record number, outliers the record's key
+struct SeedSelDev {
+    const int32_t *slot_of_local; // [nlocal] slot in the selection, -1: not selected
+    int64_t nlocal;
+    const uint64_t *okeys;        // [nsel] the selected keys ascending
+    const int32_t *oslot;         // [nsel] their slots
+    int32_t nsel;
+};
+
+__device__ __forceinline__ int sp_lane_rank(unsigned long long bal) { // kept lanes below this one (mbcnt)
+    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+}
+
+// The forward seeds [s0, s1) - numbered by `foff` ([M + 1]: the even lists md = 2 m of md_off back to back; FLAT: of out_off)
+// - of the masks [l0, l1) that hold them, as slot << 32 | loc for the seeds of selected records.  A bandwidth kernel
+// beside k_sp_dump_range: the lanes run over the seeds, a tile of blockDim.x seeds brackets its masks once
+// (lm_seed_walk.h), only the packed VALUES are read (the partition of a seed does not matter here).  Every wavefront
+// ballots "kept", its first lane reserves popcount slots with one vector atomic on *n_out, the lanes write at that base +
+// their rank; a store is guarded by `cap`.  COUNT: the atomics only (the size of the key array of a partial selection).
+template <bool FLAT, bool COUNT>
+__global__ __launch_bounds__(256) void k_sp_seed_locs(DevIndexView ix, const int64_t *__restrict__ foff, int64_t l0, int64_t l1,
+                                                       int64_t s0, int64_t s1, SeedSelDev sel, uint64_t *__restrict__ out,
+                                                       unsigned long long cap, unsigned long long *__restrict__ n_out) {
+    const int64_t *__restrict__ off = FLAT ? ix.out_off : ix.md_off;
+    const int val_bits = ix.gid_bits + ix.pos_bits + 1;
+    const uint64_t loc_mask = (1ull << (ix.pos_bits + 1)) - 1ull;
+    const int lane = (int)(threadIdx.x & 63u);
+    for (int64_t t0 = s0 + (int64_t)blockIdx.x * blockDim.x; t0 < s1; t0 += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t t1 = (t0 + (int64_t)blockDim.x < s1 ? t0 + (int64_t)blockDim.x : s1) - 1;
+        int64_t lf, ll;
+        sw_tile_lists(foff, l0, l1, t0, t1, &lf, &ll);
+        const int64_t i = t0 + threadIdx.x;
+        int32_t slot = -1;
+        uint32_t loc = 0;
+        if (i <= t1) {
+            const int64_t m = sw_last_le(foff, lf, ll, i);
+            const int64_t src = off[2 * m] + (i - foff[m]);
+            if (FLAT) {
+                const uint64_t val = ix.out_vals[src], bg = val >> 30;
+                if (!(val & 1ull) && sel.nsel > 0) {
+                    const int64_t j = sw_last_le(sel.okeys, 0, (int64_t)sel.nsel - 1, (int64_t)bg);
+                    if (sel.okeys[j] == bg) slot = sel.oslot[j];
+                }
+                loc = (uint32_t)(val >> 1) & 0x1fffffffu;
+            } else {
+                const uint64_t pv = lm_bits_get(ix.pk_vals, src, val_bits);
+                const uint64_t local = lm_packed_val_genome(pv, ix.pos_bits);
+                if ((int64_t)local < sel.nlocal) slot = sel.slot_of_local[local];
+                loc = (uint32_t)(pv & loc_mask);
+            }
+        }
+        const bool kept = slot >= 0;
+        const unsigned long long bal = __ballot(kept);
+        unsigned long long base = 0;
+        if (lane == 0 && bal) base = atomicAdd(n_out, (unsigned long long)__popcll(bal));
+        if (!COUNT) {
+            base = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(base >> 32)) << 32) |
+                   (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+            const unsigned long long o = base + (unsigned long long)sp_lane_rank(bal);
+            if (kept && o < cap) out[o] = ((uint64_t)(uint32_t)slot << 32) | loc;
+        }
+    }
+}
+
+// sorted entries -> off[nsel + 1] (first entry of every slot; a slot without entries starts where the next one does) and locs
+__global__ __launch_bounds__(256) void k_sp_seed_segment(const uint64_t *__restrict__ ent, int64_t n, int32_t nsel,
+                                                          int64_t *__restrict__ off, uint32_t *__restrict__ locs) {
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e <= n; e += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t hi = e < n ? (int64_t)(ent[e] >> 32) : (int64_t)nsel;
+        const int64_t lo = e > 0 ? (int64_t)(ent[e - 1] >> 32) + 1 : 0;
+        for (int64_t s = lo; s <= hi && s <= (int64_t)nsel; s++) off[s] = e;
+        if (e < n) locs[e] = (uint32_t)ent[e];
+    }
+}
+
+struct SdArgs {
+    const uint64_t *ent; // sorted slot << 32 | loc
+    int64_t n, ntiles;
+    const int32_t *coff;    // [nsel + 1] CSR of the contig starts of the selected records
+    const uint32_t *cstart;
+    uint32_t min_dist, hist_bins, hist_width;
+    unsigned long long *rec_max; // [nsel] dist << 32 | ~pos: the largest dist, the smallest position among equals
+    uint32_t *rec_seeded;        // [nsel] contigs with a seed
+    unsigned long long *hist;    // [hist_bins]
+    uint32_t *tile_cnt;          // [ntiles + 1] reported positions per tile of 256 entries (EMIT = false writes it)
+    const int64_t *tile_off;     // its exclusive scan (EMIT = true reads it)
+    lm_seed_dist_row *rows;
+};
+
+// One lane per sorted entry, tiles of 256 entries.  EMIT = false: per record the largest distance (reduced over the lanes
+// of a wavefront that share a record, one atomic per wavefront and record), the seeded contigs, the histogram of the
+// reported distances in LDS (flushed once per workgroup) and the number of reported entries of every tile.  EMIT = true,
+// after a scan of those numbers: the reported rows at tile offset + wavefront offset + rank among the reporting lanes -
+// the order of the sorted entries, not the arrival order of an atomic.
+template <bool EMIT> __global__ __launch_bounds__(256) void k_sd_pass(SdArgs a) {
+    extern __shared__ uint32_t sd_lds[]; // [hist_bins] (EMIT = false)
+    __shared__ uint32_t wcnt[4];
+    const int lane = (int)(threadIdx.x & 63u), w = (int)(threadIdx.x >> 6);
+    if (!EMIT) {
+        for (uint32_t b = threadIdx.x; b < a.hist_bins; b += blockDim.x) sd_lds[b] = 0;
+        __syncthreads();
+    }
+    for (int64_t ti = blockIdx.x; ti < a.ntiles; ti += gridDim.x) {
+        const int64_t e = ti * 256 + threadIdx.x;
+        const bool act = e < a.n;
+        uint32_t slot = 0, loc = 0;
+        SdEntry en = {0, 0, 0, false};
+        if (act) {
+            const uint64_t k = a.ent[e];
+            slot = (uint32_t)(k >> 32);
+            loc = (uint32_t)k;
+            uint64_t kp = 0;
+            if (e > 0) kp = a.ent[e - 1];
+            const int32_t c0 = a.coff[slot];
+            en = sd_entry(a.cstart + c0, a.coff[slot + 1] - c0, loc >> 1, e > 0 && (uint32_t)(kp >> 32) == slot, (uint32_t)kp >> 1);
+        }
+        const bool rep = act && sd_reported(en.dist, a.min_dist);
+        const unsigned long long bal = __ballot(rep);
+        if (lane == 0) wcnt[w] = (uint32_t)__popcll(bal);
+        __syncthreads();
+        if (!EMIT) {
+            if (threadIdx.x == 0) a.tile_cnt[ti] = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+            if (rep && a.hist_bins) atomicAdd(&sd_lds[sd_bin(en.dist, a.hist_bins, a.hist_width)], 1u);
+            if (act && en.first) atomicAdd(&a.rec_seeded[slot], 1u);
+            // the largest distance: the entries are sorted, so a wavefront holds a few records at most
+            const unsigned long long v = act ? ((unsigned long long)en.dist << 32) | (0xffffffffu - (loc >> 1)) : 0ull;
+            unsigned long long todo = __ballot(act);
+            while (todo) {
+                const int first = __ffsll((long long)todo) - 1;
+                const uint32_t s = (uint32_t)__shfl((int)slot, first);
+                const bool mine = act && slot == s;
+                uint32_t hi = mine ? (uint32_t)(v >> 32) : 0u, lo = mine ? (uint32_t)v : 0u;
+                for (int d = 32; d > 0; d >>= 1) {
+                    const uint32_t ohi = (uint32_t)__shfl_xor((int)hi, d), olo = (uint32_t)__shfl_xor((int)lo, d);
+                    if (ohi > hi || (ohi == hi && olo > lo)) {
+                        hi = ohi;
+                        lo = olo;
+                    }
+                }
+                if (lane == first) atomicMax(&a.rec_max[s], ((unsigned long long)hi << 32) | lo);
+                todo &= ~__ballot(mine);
+            }
+        } else if (rep) {
+            int64_t o = a.tile_off[ti] + sp_lane_rank(bal);
+            for (int x = 0; x < w; x++) o += wcnt[x];
+            lm_seed_dist_row r;
+            r.record = slot;
+            r.contig = (uint32_t)en.contig;
+            r.pos = loc >> 1;
+            r.pos_in_contig = (loc >> 1) - en.start;
+            r.strand = loc & 1u;
+            r.dist = en.dist;
+            a.rows[o] = r;
+        }
+        __syncthreads(); // (wcnt is written again by the next tile)
+    }
+    if (!EMIT) {
+        __syncthreads();
+        for (uint32_t b = threadIdx.x; b < a.hist_bins; b += blockDim.x)
+            if (sd_lds[b]) atomicAdd(&a.hist[b], (unsigned long long)sd_lds[b]);
+    }
+}
+
+__global__ void k_sd_records(const uint64_t *__restrict__ keys, const int64_t *__restrict__ off, const int32_t *__restrict__ coff,
+                             const unsigned long long *__restrict__ rec_max, const uint32_t *__restrict__ rec_seeded, int32_t nsel,
+                             lm_seed_dist_rec *__restrict__ recs) {
+    for (int32_t s = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x); s < nsel; s += (int32_t)(gridDim.x * blockDim.x)) {
+        lm_seed_dist_rec r;
+        r.key = keys[s];
+        r.seeds = off[s + 1] - off[s];
+        r.max_dist = (uint32_t)(rec_max[s] >> 32);
+        r.max_dist_pos = r.seeds > 0 ? 0xffffffffu - (uint32_t)rec_max[s] : 0u;
+        r.contigs = coff[s + 1] - coff[s];
+        r.contigs_without_seeds = r.contigs - (int32_t)rec_seeded[s];
+        recs[s] = r;
+    }
+}
+
+// the selected records' sorted entries, position lists and tables on the device
+struct SeedLists {
+    std::vector<uint64_t> keys;     // [nsel] record keys in selection order
+    std::vector<int64_t> local;     // [nsel] their local record numbers
+    DBuf<uint64_t> ent, ent2;       // ent: the sorted entries
+    DBuf<int64_t> off;              // [nsel + 1]
+    DBuf<uint32_t> locs;            // [n]
+    int64_t n = 0;
+};
+
+template <typename T> static void sp_upload(lm_index *ix, DBuf<T> &d, const std::vector<T> &v) {
+    d.alloc_exact(std::max<size_t>(v.size(), 1));
+    if (!v.empty()) HIPCHK(hipMemcpyAsync(d.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, ix->st));
+}
+
+static void seed_lists(lm_index *ix, const char *who, const uint64_t *keys, size_t nkeys, SeedLists &L) {
+    const HostIndex &h = ix->host;
+    const int64_t nlocal = (int64_t)h.genomes.size();
+    const int M = h.M;
+    const bool dbg = getenv("LM_DEBUG") != nullptr;
+    if (!keys && nkeys > 0) throw SeedArg(std::string(who) + ": keys is NULL but nkeys is not 0");
+    if (nkeys >= ((size_t)1 << 31)) throw SeedArg(std::string(who) + ": more than 2^31 keys");
+    // ---- the selection
+    const bool all = keys == nullptr;
+    std::vector<int32_t> slot_of_local((size_t)nlocal, -1);
+    if (all) {
+        for (int64_t l = 0; l < nlocal; l++) {
+            L.keys.push_back(h.genomes[(size_t)l].bg);
+            L.local.push_back(l);
+            slot_of_local[(size_t)l] = (int32_t)l;
+        }
+    } else {
+        const auto &local_of = ix->bg2local; // key -> local record, kept by the handle (lm_index_set_genome_filter uses it too)
+        for (size_t s = 0; s < nkeys; s++) {
+            const auto it = local_of.find(keys[s]);
+            const std::string name = "key " + std::to_string(keys[s]) + " (batch " + std::to_string(keys[s] >> 17) + ", index " + std::to_string(keys[s] & 0x1ffff) + ")";
+            if (it == local_of.end()) {
+                if (h.other_of.count(keys[s]))
+                    throw SeedArg(std::string(who) + ": " + name + " is a record of another shard (this handle is shard " + std::to_string(h.shard_rank) +
+                                  " of " + std::to_string(h.shard_count) + " and answers for its own records)");
+                throw SeedArg(std::string(who) + ": " + name + " is no record of this index");
+            }
+            if (slot_of_local[(size_t)it->second] >= 0) throw SeedArg(std::string(who) + ": " + name + " is given twice");
+            slot_of_local[(size_t)it->second] = (int32_t)s;
+            L.keys.push_back(keys[s]);
+            L.local.push_back((int64_t)it->second);
+        }
+    }
+    const int32_t nsel = (int32_t)L.keys.size();
+    std::vector<std::pair<uint64_t, int32_t>> sorted_keys;
+    for (int32_t s = 0; s < nsel; s++) sorted_keys.emplace_back(L.keys[(size_t)s], s);
+    std::sort(sorted_keys.begin(), sorted_keys.end());
+    std::vector<uint64_t> okeys;
+    std::vector<int32_t> oslot;
+    for (auto &e : sorted_keys) {
+        okeys.push_back(e.first);
+        oslot.push_back(e.second);
+    }
+    // ---- the forward lists numbered back to back
+    std::vector<int64_t> md_off((size_t)2 * M + 1), out_off((size_t)2 * M + 1), foff[2];
+    HIPCHK(hipMemcpyAsync(md_off.data(), ix->d_md_off.p, md_off.size() * 8, hipMemcpyDeviceToHost, ix->st));
+    HIPCHK(hipMemcpyAsync(out_off.data(), ix->d_out_off.p, out_off.size() * 8, hipMemcpyDeviceToHost, ix->st));
+    HIPCHK(hipStreamSynchronize(ix->st));
+    for (int f = 0; f < 2; f++) {
+        const std::vector<int64_t> &o = f ? out_off : md_off;
+        foff[f].assign((size_t)M + 1, 0);
+        for (int m = 0; m < M; m++) foff[f][(size_t)m + 1] = foff[f][(size_t)m] + (o[(size_t)2 * m + 1] - o[(size_t)2 * m]);
+    }
+    const int64_t nfwd[2] = {foff[0].back(), foff[1].back()};
+    DBuf<int32_t> d_slot, d_oslot;
+    DBuf<uint64_t> d_okeys;
+    DBuf<int64_t> d_foff[2];
+    DBuf<unsigned long long> d_cnt;
+    sp_upload(ix, d_slot, slot_of_local);
+    sp_upload(ix, d_okeys, okeys);
+    sp_upload(ix, d_oslot, oslot);
+    sp_upload(ix, d_foff[0], foff[0]);
+    sp_upload(ix, d_foff[1], foff[1]);
+    d_cnt.alloc_exact(1, true, ix->st);
+    const SeedSelDev sel{d_slot.p, nlocal, d_okeys.p, d_oslot.p, nsel};
+    // pieces: at most 2^26 seeds per launch as for lm_index_builder_extend; tests make them small (no result depends on it)
+    int64_t piece = (int64_t)1 << 26;
+    if (const char *e = getenv("LM_SEEDPOS_PIECE_SEEDS")) piece = std::max<int64_t>(4, atoll(e));
+    int npieces = 0;
+    auto walk = [&](bool count, uint64_t *out, unsigned long long cap) {
+        for (int f = 0; f < 2; f++)
+            for (int64_t s0 = 0; s0 < nfwd[f]; s0 += piece) {
+                const int64_t s1 = std::min(nfwd[f], s0 + piece);
+                int64_t l0, l1;
+                sw_piece_lists(foff[f].data(), M, s0, s1, &l0, &l1);
+                const unsigned grid = (unsigned)std::min<int64_t>((s1 - s0 + 255) / 256, 2048); // at most 8 workgroups per CU, then a grid stride
+#define SP_LOCS_LAUNCH(F, C) hipLaunchKernelGGL((k_sp_seed_locs<F, C>), dim3(grid), dim3(256), 0, ix->st, ix->view, d_foff[f].p, l0, l1, s0, s1, sel, out, cap, d_cnt.p)
+                if (f) {
+                    if (count) SP_LOCS_LAUNCH(true, true);
+                    else SP_LOCS_LAUNCH(true, false);
+                } else {
+                    if (count) SP_LOCS_LAUNCH(false, true);
+                    else SP_LOCS_LAUNCH(false, false);
+                }
+#undef SP_LOCS_LAUNCH
+                npieces++;
+            }
+        HIPCHK(hipGetLastError());
+        unsigned long long c = 0;
+        HIPCHK(hipMemcpyAsync(&c, d_cnt.p, sizeof c, hipMemcpyDeviceToHost, ix->st));
+        HIPCHK(hipStreamSynchronize(ix->st));
+        return (int64_t)c;
+    };
+    // ---- the size of the key array: every forward seed when every record is wanted, else a counting pass
+    const double t0 = now_ms();
+    int64_t n = nsel > 0 ? nfwd[0] + nfwd[1] : 0; // (keys given, nkeys = 0: no record, no seed, nothing is walked)
+    if (!all && nsel > 0) {
+        n = walk(true, nullptr, 0);
+        HIPCHK(hipMemsetAsync(d_cnt.p, 0, sizeof(unsigned long long), ix->st));
+    }
+    const double t1 = now_ms();
+    try {
+        L.ent.alloc_exact((size_t)n + 1);
+        L.ent2.alloc_exact((size_t)n + 1);
+        L.off.alloc_exact((size_t)nsel + 1);
+        L.locs.alloc_exact((size_t)n + 1);
+    } catch (const DeviceOOM &e) {
+        throw DeviceOOM(std::string(who) + ": the " + std::to_string(n) + " forward seeds of the selection need 2 x 8 B of sort keys and 4 B of "
+                        "position list each (" + std::to_string((n * 20) >> 20) + " MB) on the device beside the index: " + e.what());
+    }
+    npieces = 0;
+    const double t1b = now_ms(); // (the allocations are not the extract kernel's time)
+    const int64_t got = nsel > 0 ? walk(false, L.ent2.p, (unsigned long long)n) : 0;
+    if (got != n) throw HipError(std::string(who) + ": the image holds " + std::to_string(got) + " forward seeds of the selection where " + std::to_string(n) + " were counted");
+    const double t2 = now_ms();
+    try {
+        prim_sort_keys(ix->st, ix->tmp, L.ent2.p, L.ent.p, (size_t)n, 0, 32 + bits_for(std::max<int64_t>(nsel, 2)));
+    } catch (const DeviceOOM &e) {
+        throw DeviceOOM(std::string(who) + ": the radix sort of " + std::to_string(n) + " keys needs scratch beside its two key arrays: " + e.what());
+    }
+    if (dbg) HIPCHK(hipStreamSynchronize(ix->st));
+    const double t3 = now_ms();
+    hipLaunchKernelGGL(k_sp_seed_segment, dim3(sp_grid(n + 1)), dim3(256), 0, ix->st, L.ent.p, n, nsel, L.off.p, L.locs.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ix->st));
+    L.ent2.release(); // (the unsorted keys: the distance pass allocates its rows in their place)
+    L.n = n;
+    if (dbg) {
+        const double rd = (double)nfwd[0] * (ix->view.gid_bits + ix->view.pos_bits + 1) / 8.0 + (double)nfwd[1] * 8.0;
+        fprintf(stderr, "[lm] seed positions: %d records, %lld of %lld + %lld forward seeds (main + outlier): count %.3f ms, allocations %.3f ms, "
+                        "extract %.3f ms (%d pieces of %lld, %.0f bytes of values read, %.1f GB/s), sort %.3f ms, segment %.3f ms\n",
+                (int)nsel, (long long)n, (long long)nfwd[0], (long long)nfwd[1], t1 - t0, t1b - t1, t2 - t1b, npieces, (long long)piece, rd,
+                rd / std::max(1e-6, t2 - t1b) / 1e6, t3 - t2, now_ms() - t3);
+    }
+}
+
+} // namespace lm
+
+struct lm_seedpos {
+    std::vector<uint64_t> keys;
+    std::vector<int64_t> off;
+    std::vector<uint32_t> locs;
+};
+struct lm_seed_dist {
+    std::vector<lm_seed_dist_rec> recs;
+    std::vector<uint64_t> hist;
+    std::vector<lm_seed_dist_row> rows;
+};
+
+// runs `body` under the index lock; refusals and failures become a status and a text on the handle
+template <typename Body> static lm_status seed_call(lm_index *ix, Body body) {
+    std::lock_guard<std::mutex> lock(ix->mu);
+    try {
+        HIPCHK(hipSetDevice(ix->device));
+        body();
+        return LM_OK;
+    } catch (const lm::SeedArg &e) {
+        ix->err = e.what();
+        return LM_ERR_ARG;
+    } catch (const DeviceOOM &e) {
+        (void)hipGetLastError();
+        ix->err = e.what();
+        return LM_ERR_NOMEM;
+    } catch (const std::bad_alloc &) {
+        ix->err = "seed positions: the host could not hold the result";
+        return LM_ERR_NOMEM;
+    } catch (const std::exception &e) {
+        ix->err = e.what();
+        return LM_ERR_HIP;
+    }
+}
+
+extern "C" lm_status lm_index_seed_positions(lm_index *ix, const uint64_t *keys, size_t nkeys, lm_seedpos **out) {
+    if (!ix || !out) return LM_ERR_ARG;
+    *out = nullptr;
+    std::unique_ptr<lm_seedpos> res(new lm_seedpos());
+    const lm_status st = seed_call(ix, [&]() {
+        lm::SeedLists L;
+        lm::seed_lists(ix, "lm_index_seed_positions", keys, nkeys, L);
+        res->keys = L.keys;
+        res->off.resize(L.keys.size() + 1);
+        res->locs.resize((size_t)L.n);
+        HIPCHK(hipMemcpyAsync(res->off.data(), L.off.p, res->off.size() * 8, hipMemcpyDeviceToHost, ix->st));
+        if (L.n > 0) HIPCHK(hipMemcpyAsync(res->locs.data(), L.locs.p, (size_t)L.n * 4, hipMemcpyDeviceToHost, ix->st));
+        HIPCHK(hipStreamSynchronize(ix->st));
+    });
+    if (st == LM_OK) *out = res.release();
+    return st;
+}
+extern "C" size_t lm_seedpos_get(const lm_seedpos *sp, const uint64_t **keys, const int64_t **off, const uint32_t **locs) {
+    if (!sp) return 0;
+    if (keys) *keys = sp->keys.data();
+    if (off) *off = sp->off.data();
+    if (locs) *locs = sp->locs.data();
+    return sp->keys.size();
+}
+extern "C" void lm_seedpos_free(lm_seedpos *sp) { delete sp; }
+
+extern "C" lm_status lm_index_seed_distances(lm_index *ix, const uint64_t *keys, size_t nkeys, const lm_seed_dist_opt *opt_in, lm_seed_dist **out) {
+    using namespace lm;
+    if (!ix || !out) return LM_ERR_ARG;
+    *out = nullptr;
+    lm_seed_dist_opt opt = {0, 0, 0, 0};
+    if (opt_in) opt = *opt_in;
+    std::unique_ptr<lm_seed_dist> res(new lm_seed_dist());
+    const lm_status st = seed_call(ix, [&]() {
+        if (opt.hist_bins > 0 && opt.hist_width < 1) throw SeedArg("lm_index_seed_distances: hist_bins = " + std::to_string(opt.hist_bins) + " with hist_width < 1");
+        if (opt.hist_bins > 4096) throw SeedArg("lm_index_seed_distances: hist_bins = " + std::to_string(opt.hist_bins) + " (at most 4096 counters)");
+        SeedLists L;
+        seed_lists(ix, "lm_index_seed_distances", keys, nkeys, L);
+        const HostIndex &h = ix->host;
+        const int32_t nsel = (int32_t)L.keys.size();
+        // ---- the contig starts of the selected records as a CSR
+        std::vector<int32_t> coff((size_t)nsel + 1, 0);
+        std::vector<uint32_t> cstart;
+        for (int32_t s = 0; s < nsel; s++) {
+            const HostGenome &G = h.genomes[(size_t)L.local[(size_t)s]];
+            const int32_t nc = std::max<int32_t>(1, (int32_t)G.seq_sizes.size());
+            const size_t at = cstart.size();
+            cstart.resize(at + (size_t)nc, 0u);
+            if (!G.seq_sizes.empty()) sd_contig_starts(G.seq_sizes.data(), nc, h.contig_interval, cstart.data() + at);
+            coff[(size_t)s + 1] = (int32_t)cstart.size();
+        }
+        const int64_t n = L.n, ntiles = (n + 255) / 256;
+        DBuf<int32_t> d_coff;
+        DBuf<uint32_t> d_cstart, d_seeded, d_tile_cnt;
+        DBuf<uint64_t> d_keys;
+        DBuf<unsigned long long> d_max, d_hist;
+        DBuf<int64_t> d_tile_off;
+        DBuf<lm_seed_dist_rec> d_recs;
+        DBuf<lm_seed_dist_row> d_rows;
+        sp_upload(ix, d_coff, coff);
+        sp_upload(ix, d_cstart, cstart);
+        sp_upload(ix, d_keys, L.keys);
+        d_seeded.alloc_exact((size_t)nsel, true, ix->st);
+        d_max.alloc_exact((size_t)nsel, true, ix->st);
+        d_hist.alloc_exact(std::max<size_t>(opt.hist_bins, 1), true, ix->st);
+        d_tile_cnt.alloc_exact((size_t)ntiles + 1, true, ix->st);
+        d_tile_off.alloc_exact((size_t)ntiles + 1, true, ix->st);
+        d_recs.alloc_exact((size_t)nsel);
+        SdArgs a{L.ent.p, n, ntiles, d_coff.p, d_cstart.p, opt.min_dist, opt.hist_bins, opt.hist_width, d_max.p, d_seeded.p, d_hist.p,
+                 d_tile_cnt.p, d_tile_off.p, nullptr};
+        const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ntiles, 2048));
+        int64_t nrows = 0;
+        if (n > 0) {
+            hipLaunchKernelGGL(k_sd_pass<false>, dim3(grid), dim3(256), (size_t)opt.hist_bins * 4, ix->st, a);
+            HIPCHK(hipGetLastError());
+            prim_scan_to_i64(ix->st, ix->tmp, d_tile_cnt.p, (size_t)ntiles, d_tile_off.p);
+            HIPCHK(hipMemcpyAsync(&nrows, d_tile_off.p + ntiles, sizeof nrows, hipMemcpyDeviceToHost, ix->st));
+            HIPCHK(hipStreamSynchronize(ix->st));
+        }
+        hipLaunchKernelGGL(k_sd_records, dim3(sp_grid(nsel)), dim3(256), 0, ix->st, d_keys.p, L.off.p, d_coff.p, d_max.p, d_seeded.p, nsel, d_recs.p);
+        HIPCHK(hipGetLastError());
+        if (nrows > 0) {
+            try {
+                d_rows.alloc_exact((size_t)nrows);
+            } catch (const DeviceOOM &e) {
+                throw DeviceOOM("lm_index_seed_distances: the " + std::to_string(nrows) + " reported rows (24 B each) do not fit on the device beside the "
+                                "index and the sorted positions (a larger min_dist reports fewer): " + e.what());
+            }
+            a.rows = d_rows.p;
+            hipLaunchKernelGGL(k_sd_pass<true>, dim3(grid), dim3(256), 0, ix->st, a);
+            HIPCHK(hipGetLastError());
+        }
+        res->recs.resize((size_t)nsel);
+        res->hist.resize(opt.hist_bins);
+        res->rows.resize((size_t)nrows);
+        if (nsel > 0) HIPCHK(hipMemcpyAsync(res->recs.data(), d_recs.p, (size_t)nsel * sizeof(lm_seed_dist_rec), hipMemcpyDeviceToHost, ix->st));
+        if (opt.hist_bins > 0) HIPCHK(hipMemcpyAsync(res->hist.data(), d_hist.p, (size_t)opt.hist_bins * 8, hipMemcpyDeviceToHost, ix->st));
+        if (nrows > 0) HIPCHK(hipMemcpyAsync(res->rows.data(), d_rows.p, (size_t)nrows * sizeof(lm_seed_dist_row), hipMemcpyDeviceToHost, ix->st));
+        HIPCHK(hipStreamSynchronize(ix->st));
+    });
+    if (st == LM_OK) *out = res.release();
+    return st;
+}
+extern "C" size_t lm_seed_dist_records(const lm_seed_dist *sd, const lm_seed_dist_rec **recs) {
+    if (!sd) return 0;
+    if (recs) *recs = sd->recs.data();
+    return sd->recs.size();
+}
+extern "C" size_t lm_seed_dist_hist(const lm_seed_dist *sd, const uint64_t **hist) {
+    if (!sd) return 0;
+    if (hist) *hist = sd->hist.data();
+    return sd->hist.size();
+}
+extern "C" size_t lm_seed_dist_rows(const lm_seed_dist *sd, const lm_seed_dist_row **rows) {
+    if (!sd) return 0;
+    if (rows) *rows = sd->rows.data();
+    return sd->rows.size();
+}
+extern "C" void lm_seed_dist_free(lm_seed_dist *sd) { delete sd; }
 
 // ---- the HBM image written back to disk -----------------------------------------------------------------------------------
 // `lexicmap index` output as the reference lays it out, EXCEPT masks.bin, which is written in this
