@@ -33,7 +33,7 @@
 namespace lm {
 
 static inline void bsync(lm_index *ix) {
-    hipError_t e = hipStreamSynchronize(ix->st);
+    hipError_t e = hipStreamSynchronize(ix->lane[0].main.st);
     if (e != hipSuccess) throw HipError(std::string("builder sync: ") + hipGetErrorString(e));
 }
 
@@ -687,7 +687,7 @@ struct lm_index_builder {
     ~lm_index_builder() {
         if (ix) {
             (void)hipSetDevice(ix->device);
-            if (ix->st) (void)hipStreamSynchronize(ix->st);
+            if (ix->lane[0].main.st) (void)hipStreamSynchronize(ix->lane[0].main.st);
         }
         slabs.clear();
         if (ix) lm_index_close(ix);
@@ -699,12 +699,13 @@ namespace lm {
 // packs one record into the growing store (its slot: build_slot_bytes, zero-padded); returns its byte offset in the final store
 static int64_t builder_pack(lm_index_builder *b, const BuildRecord &r, const lm_contig *contigs) {
     lm_index *ix = b->ix;
+    const hipStream_t st = ix->lane[0].main.st;
     const int64_t slot = build_slot_bytes(r.len);
     if (b->slabs.empty() || b->slabs.back()->used + slot > b->slabs.back()->cap) {
         std::unique_ptr<lm_index_builder::Slab> s(new lm_index_builder::Slab());
         s->cap = std::max<int64_t>(b->slab_bytes, slot);
         s->first = b->store_bytes;
-        s->d.alloc_exact((size_t)s->cap + 64, true, ix->st);
+        s->d.alloc_exact((size_t)s->cap + 64, true, st);
         b->slabs.push_back(std::move(s));
     }
     lm_index_builder::Slab &sl = *b->slabs.back();
@@ -724,13 +725,13 @@ static int64_t builder_pack(lm_index_builder *b, const BuildRecord &r, const lm_
     b->d_src.ensure((size_t)r.n);
     b->d_dst.ensure((size_t)r.n);
     b->d_len.ensure((size_t)r.n);
-    if (total > 0) HIPCHK(hipMemcpyAsync(b->d_ascii.p, b->stage.p, (size_t)total, hipMemcpyHostToDevice, ix->st));
-    HIPCHK(hipMemcpyAsync(b->d_src.p, src.data(), (size_t)r.n * 8, hipMemcpyHostToDevice, ix->st));
-    HIPCHK(hipMemcpyAsync(b->d_dst.p, r.dst_off.data(), (size_t)r.n * 4, hipMemcpyHostToDevice, ix->st));
-    HIPCHK(hipMemcpyAsync(b->d_len.p, len.data(), (size_t)r.n * 4, hipMemcpyHostToDevice, ix->st));
+    if (total > 0) HIPCHK(hipMemcpyAsync(b->d_ascii.p, b->stage.p, (size_t)total, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b->d_src.p, src.data(), (size_t)r.n * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b->d_dst.p, r.dst_off.data(), (size_t)r.n * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b->d_len.p, len.data(), (size_t)r.n * 4, hipMemcpyHostToDevice, st));
     // (a slab is zeroed when it is cut, but a genome that failed half way may have been here before: the padding must be zero)
-    HIPCHK(hipMemsetAsync(sl.d.p + sl.used, 0, (size_t)slot, ix->st));
-    hipLaunchKernelGGL(k_pack_record, dim3(gridn(((int64_t)r.len + 3) >> 2)), dim3(256), 0, ix->st, b->d_ascii.p, b->d_src.p, b->d_dst.p,
+    HIPCHK(hipMemsetAsync(sl.d.p + sl.used, 0, (size_t)slot, st));
+    hipLaunchKernelGGL(k_pack_record, dim3(gridn(((int64_t)r.len + 3) >> 2)), dim3(256), 0, st, b->d_ascii.p, b->d_src.p, b->d_dst.p,
                        b->d_len.p, r.n, r.len, sl.d.p + sl.used);
     HIPCHK(hipGetLastError());
     bsync(ix);
@@ -777,7 +778,7 @@ static bool build_opt_ok(const char *who, const lm_build_opt &bo, std::string &e
 // LM_OK, or the status to return with its text in g_open_error.
 static lm_status builder_header(lm_index *ix, int K, int M, int64_t mask_seed, int contig_interval, const HostIndex *bh, std::vector<int32_t> &pfx) {
     HIPCHK(hipSetDevice(ix->device));
-    HIPCHK(hipStreamCreate(&ix->st));
+    HIPCHK(hipStreamCreate(&ix->lane[0].main.st));
     const lm_options &opt = ix->opt;
     HostIndex &h = ix->host;
     const int p = bh ? bh->mask_prefix : mask_prefix_of(M);
@@ -812,8 +813,8 @@ static lm_status builder_header(lm_index *ix, int K, int M, int64_t mask_seed, i
     }
     ix->d_masks.ensure((size_t)M);
     ix->d_pfx_first.ensure(pfx.size());
-    HIPCHK(hipMemcpyAsync(ix->d_masks.p, h.masks.data(), (size_t)M * 8, hipMemcpyHostToDevice, ix->st));
-    HIPCHK(hipMemcpyAsync(ix->d_pfx_first.p, pfx.data(), pfx.size() * 4, hipMemcpyHostToDevice, ix->st));
+    HIPCHK(hipMemcpyAsync(ix->d_masks.p, h.masks.data(), (size_t)M * 8, hipMemcpyHostToDevice, ix->lane[0].main.st));
+    HIPCHK(hipMemcpyAsync(ix->d_pfx_first.p, pfx.data(), pfx.size() * 4, hipMemcpyHostToDevice, ix->lane[0].main.st));
     bsync(ix);
     return LM_OK;
 }
@@ -841,6 +842,7 @@ static void build_seed_index(lm_index *ix, const std::vector<int32_t> &pfx, cons
                              const std::vector<int32_t> &reg_e, int max_desert, int seed_dist, int64_t chunk_records, int64_t chunk_bases,
                              const std::vector<SeedSource> &sources, const std::vector<uint8_t> &borrowed, const lm_res_request &rq) {
     HostIndex &h = ix->host;
+    const hipStream_t st = ix->lane[0].main.st;
     const int K = h.k, M = h.M, p = h.mask_prefix;
     const int64_t nlocal = (int64_t)h.genomes.size();
     const bool dbg = getenv("LM_DEBUG") != nullptr;
@@ -854,7 +856,7 @@ static void build_seed_index(lm_index *ix, const std::vector<int32_t> &pfx, cons
     }
     auto copy_up = [&](auto &dbuf, const auto &vec) {
         dbuf.ensure(std::max<size_t>(vec.size(), 1));
-        if (!vec.empty()) HIPCHK(hipMemcpyAsync(dbuf.p, vec.data(), vec.size() * sizeof(vec[0]), hipMemcpyHostToDevice, ix->st));
+        if (!vec.empty()) HIPCHK(hipMemcpyAsync(dbuf.p, vec.data(), vec.size() * sizeof(vec[0]), hipMemcpyHostToDevice, st));
     };
     // ---- tables
     std::vector<int64_t> goff((size_t)nlocal), slot((size_t)nlocal);
@@ -962,8 +964,8 @@ static void build_seed_index(lm_index *ix, const std::vector<int32_t> &pfx, cons
         std::unique_ptr<SrcTabs> t(new SrcTabs());
         t->md_off.resize((size_t)2 * M + 1);
         t->out_off.resize((size_t)2 * M + 1);
-        HIPCHK(hipMemcpyAsync(t->md_off.data(), S.ix->d_md_off.p, t->md_off.size() * 8, hipMemcpyDeviceToHost, ix->st));
-        HIPCHK(hipMemcpyAsync(t->out_off.data(), S.ix->d_out_off.p, t->out_off.size() * 8, hipMemcpyDeviceToHost, ix->st));
+        HIPCHK(hipMemcpyAsync(t->md_off.data(), S.ix->d_md_off.p, t->md_off.size() * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(t->out_off.data(), S.ix->d_out_off.p, t->out_off.size() * 8, hipMemcpyDeviceToHost, st));
         if (S.new_bg) {
             if ((int64_t)S.new_bg->size() != S.ix->view.ngenomes) throw HipError("index build: a source's key table does not match its records");
             copy_up(t->new_bg, *S.new_bg);
@@ -1002,16 +1004,16 @@ static void build_seed_index(lm_index *ix, const std::vector<int32_t> &pfx, cons
     auto generate = [&](const Chunk &c, unsigned long long &nseeds) {
         const unsigned long long pos_lim = pos_cap - (unsigned long long)c.n - 1;
         const double ta = now_ms();
-        HIPCHK(hipMemsetAsync(counters.p, 0, 2 * sizeof(unsigned long long), ix->st));
+        HIPCHK(hipMemsetAsync(counters.p, 0, 2 * sizeof(unsigned long long), st));
         if (lds_capture)
-            hipLaunchKernelGGL(k_capture_g<true>, dim3(c.n), dim3(1024), lds_bytes, ix->st, gt, mt, ix->d_gbits.p, c.l0, dbl_map.p, dbl_cnt.p,
+            hipLaunchKernelGGL(k_capture_g<true>, dim3(c.n), dim3(1024), lds_bytes, st, gt, mt, ix->d_gbits.p, c.l0, dbl_map.p, dbl_cnt.p,
                                hashes.p, miss_pos.p, miss_cnt.p, s_mask.p, s_kmer.p, s_val.p, counters.p, cap, pos_keys.p, counters.p + 1, pos_lim, dbg ? counters.p + 4 : nullptr);
         else
-            hipLaunchKernelGGL(k_capture_g<false>, dim3(c.n), dim3(1024), lds_bytes, ix->st, gt, mt, ix->d_gbits.p, c.l0, dbl_map.p, dbl_cnt.p,
+            hipLaunchKernelGGL(k_capture_g<false>, dim3(c.n), dim3(1024), lds_bytes, st, gt, mt, ix->d_gbits.p, c.l0, dbl_map.p, dbl_cnt.p,
                                hashes.p, miss_pos.p, miss_cnt.p, s_mask.p, s_kmer.p, s_val.p, counters.p, cap, pos_keys.p, counters.p + 1, pos_lim, dbg ? counters.p + 4 : nullptr);
         HIPCHK(hipGetLastError());
         unsigned long long hc[8];
-        HIPCHK(hipMemcpyAsync(hc, counters.p, sizeof hc, hipMemcpyDeviceToHost, ix->st));
+        HIPCHK(hipMemcpyAsync(hc, counters.p, sizeof hc, hipMemcpyDeviceToHost, st));
         bsync(ix);
         const double tb = now_ms();
         t_cap += tb - ta;
@@ -1025,22 +1027,22 @@ static void build_seed_index(lm_index *ix, const std::vector<int32_t> &pfx, cons
             return false;
         }
         unsigned long long npk = hc[1];
-        hipLaunchKernelGGL(k_pseudo_pos_g, dim3((c.n + 63) / 64), dim3(64), 0, ix->st, gt, c.l0, c.n, K, pos_keys.p, npk);
+        hipLaunchKernelGGL(k_pseudo_pos_g, dim3((c.n + 63) / 64), dim3(64), 0, st, gt, c.l0, c.n, K, pos_keys.p, npk);
         npk += (unsigned long long)c.n;
-        prim_sort_keys(ix->st, ix->tmp, pos_keys.p, pos_keys2.p, (size_t)npk, 0, 64);
-        hipLaunchKernelGGL(k_desert_fill_g, dim3(gridn(((int64_t)npk + 63) / 64, 4)), dim3(256), 0, ix->st, gt, mt, ix->d_gbits.p, c.l0,
+        prim_sort_keys(st, ix->lane[0].main.tmp, pos_keys.p, pos_keys2.p, (size_t)npk, 0, 64);
+        hipLaunchKernelGGL(k_desert_fill_g, dim3(gridn(((int64_t)npk + 63) / 64, 4)), dim3(256), 0, st, gt, mt, ix->d_gbits.p, c.l0,
                            pos_keys2.p, (int64_t)npk, max_desert, seed_dist, s_mask.p, s_kmer.p, s_val.p, counters.p, cap);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(hc, counters.p, sizeof hc, hipMemcpyDeviceToHost, ix->st));
+        HIPCHK(hipMemcpyAsync(hc, counters.p, sizeof hc, hipMemcpyDeviceToHost, st));
         bsync(ix);
         if (hc[0] >= cap) {
             cap = hc[0] * 3 + 65536;
             return false;
         }
         const unsigned long long upto = hc[0];
-        hipLaunchKernelGGL(k_reverse_seeds, dim3(gridn((int64_t)upto)), dim3(256), 0, ix->st, mt, 0ull, upto, s_mask.p, s_kmer.p, s_val.p,
+        hipLaunchKernelGGL(k_reverse_seeds, dim3(gridn((int64_t)upto)), dim3(256), 0, st, mt, 0ull, upto, s_mask.p, s_kmer.p, s_val.p,
                            counters.p, cap);
-        HIPCHK(hipMemcpyAsync(hc, counters.p, sizeof hc, hipMemcpyDeviceToHost, ix->st));
+        HIPCHK(hipMemcpyAsync(hc, counters.p, sizeof hc, hipMemcpyDeviceToHost, st));
         bsync(ix);
         if (hc[0] >= cap) {
             cap = hc[0] + hc[0] / 4 + 65536;
@@ -1069,11 +1071,11 @@ static void build_seed_index(lm_index *ix, const std::vector<int32_t> &pfx, cons
                 for (int64_t s0 = 0; s0 < total; s0 += piece) {
                     int64_t n = std::min<int64_t>(piece, total - s0);
                     const double td0 = dbg ? (bsync(ix), now_ms()) : 0;
-                    if (n_out) HIPCHK(hipMemsetAsync(n_out, 0, sizeof(unsigned long long), ix->st));
-                    sp_dump_range(S.ix, ix->st, flat ? T.out_off : T.md_off, flat != 0, s0, s0 + n, s_mask.p, s_kmer.p, s_val.p, nbg, n_out);
+                    if (n_out) HIPCHK(hipMemsetAsync(n_out, 0, sizeof(unsigned long long), st));
+                    sp_dump_range(S.ix, st, flat ? T.out_off : T.md_off, flat != 0, s0, s0 + n, s_mask.p, s_kmer.p, s_val.p, nbg, n_out);
                     if (n_out) {
                         unsigned long long got = 0;
-                        HIPCHK(hipMemcpyAsync(&got, n_out, sizeof got, hipMemcpyDeviceToHost, ix->st));
+                        HIPCHK(hipMemcpyAsync(&got, n_out, sizeof got, hipMemcpyDeviceToHost, st));
                         bsync(ix);
                         if (got > (unsigned long long)n) throw HipError("index build: a compacted decode piece holds more seeds than were decoded");
                         n = (int64_t)got;
@@ -1128,7 +1130,7 @@ static void build_seed_index(lm_index *ix, const std::vector<int32_t> &pfx, cons
         fprintf(stderr, "[lm] builder: partition sort %.1f ms; %lld records, %lld seeds (%lld outliers), %.2f B/seed; seed pipeline %.1f ms\n",
                 now_ms() - tf, (long long)nlocal, (long long)ix->n_seeds, (long long)ix->n_seeds_outlier,
                 (double)ix->seed_bytes / std::max<double>(1.0, (double)ix->n_seeds), now_ms() - t0);
-    ix->tmp.release();
+    ix->lane[0].main.tmp.release();
     // ---- residency: the set is built in HBM as ever; the records beyond the budget then move to pinned host memory and the
     // device store shrinks to the rest (a set that does not fit the device DURING the build is out of reach of this form)
     ix->res.genomes_device = nlocal;
@@ -1158,15 +1160,15 @@ static void build_seed_index(lm_index *ix, const std::vector<int32_t> &pfx, cons
             for (int64_t l = keep; l < nlocal; l++) { // (pinned destination: DMA at the link's rate, one copy per record)
                 const GenomePlace &pl = plan.place[(size_t)l];
                 HIPCHK(hipMemcpyAsync(ix->g_host_segs[(size_t)pl.seg].p + pl.off, ix->d_gbits.p + goff[(size_t)l], (size_t)nbs[(size_t)(l - keep)],
-                                      hipMemcpyDeviceToHost, ix->st));
+                                      hipMemcpyDeviceToHost, st));
                 h.genomes[(size_t)l].bits_off = -1; // (not in the device store)
                 goff[(size_t)l] = -1;
             }
             bsync(ix);
             {   // the device store shrinks to the records that stay (same offsets: they are its first bytes)
                 DBuf<uint8_t> kept;
-                kept.alloc_exact((size_t)kept_bytes + 64, true, ix->st);
-                if (kept_bytes > 0) HIPCHK(hipMemcpyAsync(kept.p, ix->d_gbits.p, (size_t)kept_bytes, hipMemcpyDeviceToDevice, ix->st));
+                kept.alloc_exact((size_t)kept_bytes + 64, true, st);
+                if (kept_bytes > 0) HIPCHK(hipMemcpyAsync(kept.p, ix->d_gbits.p, (size_t)kept_bytes, hipMemcpyDeviceToDevice, st));
                 bsync(ix);
                 ix->d_gbits.release();
                 std::swap(ix->d_gbits.p, kept.p);
@@ -1186,13 +1188,14 @@ static void build_seed_index(lm_index *ix, const std::vector<int32_t> &pfx, cons
 // then the seed pipeline
 static void builder_finish(lm_index_builder *b) {
     lm_index *ix = b->ix;
+    const hipStream_t st = ix->lane[0].main.st;
     HostIndex &h = ix->host;
     const lm_build_opt &bo = b->bo;
     // ---- the store: one allocation, the slabs copied to their places (they ARE consecutive pieces of it) and released
     b->d_ascii.release();
-    ix->d_gbits.alloc_exact((size_t)b->store_bytes + 64, true, ix->st);
+    ix->d_gbits.alloc_exact((size_t)b->store_bytes + 64, true, st);
     for (auto &s : b->slabs)
-        if (s->used > 0) HIPCHK(hipMemcpyAsync(ix->d_gbits.p + s->first, s->d.p, (size_t)s->used, hipMemcpyDeviceToDevice, ix->st));
+        if (s->used > 0) HIPCHK(hipMemcpyAsync(ix->d_gbits.p + s->first, s->d.p, (size_t)s->used, hipMemcpyDeviceToDevice, st));
     bsync(ix);
     b->slabs.clear();
     const lm_index *base = b->base;
@@ -1203,7 +1206,7 @@ static void builder_finish(lm_index_builder *b) {
         const lm_index *src = S.ix;
         int64_t run_src = -1, run_dst = 0, run_len = 0;
         auto flush = [&]() {
-            if (run_src >= 0) HIPCHK(hipMemcpyAsync(ix->d_gbits.p + run_dst, src->d_gbits.p + run_src, (size_t)run_len, hipMemcpyDeviceToDevice, ix->st));
+            if (run_src >= 0) HIPCHK(hipMemcpyAsync(ix->d_gbits.p + run_dst, src->d_gbits.p + run_src, (size_t)run_len, hipMemcpyDeviceToDevice, st));
             run_src = -1;
         };
         for (const auto &sd : S.recs) {
@@ -1212,7 +1215,7 @@ static void builder_finish(lm_index_builder *b) {
             const uint8_t *hp = src->g_hhost.empty() ? nullptr : src->g_hhost[(size_t)sd.first];
             if (hp) {
                 flush();
-                HIPCHK(hipMemcpyAsync(ix->d_gbits.p + G.bits_off, hp, (size_t)nb, hipMemcpyHostToDevice, ix->st));
+                HIPCHK(hipMemcpyAsync(ix->d_gbits.p + G.bits_off, hp, (size_t)nb, hipMemcpyHostToDevice, st));
                 continue;
             }
             if (run_src >= 0 && so - run_src == G.bits_off - run_dst && so >= run_src + run_len) {
@@ -1564,7 +1567,7 @@ lm_status lm_index_builder_add(lm_index_builder *b, const char *genome_id, const
             }
         } catch (const std::exception &e) {
             b->err = e.what();
-            if (hipStreamSynchronize(ix->st) != hipSuccess) b->broken = true;
+            if (hipStreamSynchronize(ix->lane[0].main.st) != hipSuccess) b->broken = true;
             (void)hipGetLastError();
             b->slabs.resize(nslabs0);
             if (nslabs0) b->slabs.back()->used = used0;
@@ -1713,11 +1716,11 @@ lm_status lm_index_build_synthetic_ex(const lm_synth_spec *spec, const lm_option
         sp.nblk = (spec->genome_len + 511) >> 9;
         sp.gbytes = build_slot_bytes(spec->genome_len);
         ix->d_gbits.alloc_exact((size_t)(nlocal * sp.gbytes) + 64);
-        HIPCHK(hipMemsetAsync(ix->d_gbits.p, 0, (size_t)(nlocal * sp.gbytes) + 64, ix->st));
+        HIPCHK(hipMemsetAsync(ix->d_gbits.p, 0, (size_t)(nlocal * sp.gbytes) + 64, ix->lane[0].main.st));
         DBuf<int16_t> shifts;
         shifts.ensure((size_t)(nlocal * sp.nblk) + 1);
-        hipLaunchKernelGGL(k_synth_shifts, dim3(gridn(nlocal, 64)), dim3(64), 0, ix->st, sp, shifts.p);
-        hipLaunchKernelGGL(k_synth_genomes, dim3(gridn(nlocal * (((int64_t)spec->genome_len + 3) >> 2))), dim3(256), 0, ix->st,
+        hipLaunchKernelGGL(k_synth_shifts, dim3(gridn(nlocal, 64)), dim3(64), 0, ix->lane[0].main.st, sp, shifts.p);
+        hipLaunchKernelGGL(k_synth_genomes, dim3(gridn(nlocal * (((int64_t)spec->genome_len + 3) >> 2))), dim3(256), 0, ix->lane[0].main.st,
                            sp, shifts.p, ix->d_gbits.p);
         bsync(ix);
         shifts.release();
@@ -1763,8 +1766,8 @@ lm_status lm_index_fetch(lm_index *ix, int64_t local_genome, int64_t start, int6
         d.ensure((size_t)len + 1);
         // (a host-resident genome is read where it lives: this kernel and k_stage_genome_bits are the two that may)
         const uint8_t *gsrc = !ix->g_hptr.empty() && ix->g_hptr[(size_t)local_genome] ? ix->g_hptr[(size_t)local_genome] : ix->d_gbits.p + G.bits_off;
-        hipLaunchKernelGGL(k_fetch_bases, dim3(gridn(len)), dim3(256), 0, ix->st, gsrc, start, len, d.p);
-        HIPCHK(hipMemcpyAsync(out, d.p, (size_t)len, hipMemcpyDeviceToHost, ix->st));
+        hipLaunchKernelGGL(k_fetch_bases, dim3(gridn(len)), dim3(256), 0, ix->lane[0].main.st, gsrc, start, len, d.p);
+        HIPCHK(hipMemcpyAsync(out, d.p, (size_t)len, hipMemcpyDeviceToHost, ix->lane[0].main.st));
         bsync(ix);
     } catch (const std::exception &e) {
         ix->err = e.what();

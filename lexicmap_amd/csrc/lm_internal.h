@@ -268,9 +268,18 @@ struct LaneSlabs {
     int64_t bytes() const { return (int64_t)(size[0] + size[1]); }
     ~LaneSlabs() { drop(); }
 };
-// the arena (and the stream) of the search running on this thread; null outside lm_search_*: plain device allocations
-inline thread_local ScratchArena *tls_arena = nullptr;
-inline thread_local hipStream_t tls_stream = nullptr;
+template <typename T> struct DBuf;
+// What the host thread works for while it runs part of a search: one of the handle's lanes, the stream its helpers launch on
+// (S(ix)) with that stream's rocPRIM storage (TMP(ix)), and the arena its phase buffers are carved from.  An unbound thread
+// (every entry point outside lm_search_*) gets lane 0's main stream and storage and plain device allocations.  Only BindScope
+// (below lm_index) writes it.
+struct ThreadBind {
+    int lane = 0;
+    hipStream_t stream = nullptr;
+    DBuf<uint8_t> *tmp = nullptr;
+    ScratchArena *arena = nullptr;
+};
+inline thread_local ThreadBind tls_bind;
 
 template <typename T> struct DBuf {
     T *p = nullptr;
@@ -287,20 +296,20 @@ template <typename T> struct DBuf {
     void ensure(size_t n) {
         if (n <= cap && p) return;
         if (p && arena) { // the block goes back while earlier launches of this thread may still read it
-            if (tls_stream) (void)hipStreamSynchronize(tls_stream); else (void)hipDeviceSynchronize();
+            if (tls_bind.stream) (void)hipStreamSynchronize(tls_bind.stream); else (void)hipDeviceSynchronize();
         }
         release();
         size_t want = std::max<size_t>(n + n / 8, 64);
-        if (phase && tls_arena && (arena_always || want * sizeof(T) >= ARENA_MIN)) {
-            p = (T *)tls_arena->alloc(want * sizeof(T));
-            arena = tls_arena;
+        if (phase && tls_bind.arena && (arena_always || want * sizeof(T) >= ARENA_MIN)) {
+            p = (T *)tls_bind.arena->alloc(want * sizeof(T));
+            arena = tls_bind.arena;
         } else {
             hipError_t e = lm_guarded_malloc((void **)&p, want * sizeof(T));
             if (e != hipSuccess) {
                 p = nullptr;
                 (void)hipGetLastError();
-                if (tls_arena) { // memory parked in empty slabs
-                    tls_arena->trim();
+                if (tls_bind.arena) { // memory parked in empty slabs
+                    tls_bind.arena->trim();
                     e = lm_guarded_malloc((void **)&p, want * sizeof(T));
                 }
             }
@@ -406,6 +415,26 @@ namespace lm {
 struct Work;
 struct AlignCtx;
 
+// a stream and the rocPRIM temporary storage of the calls made on it
+struct StreamCtx {
+    hipStream_t st = nullptr; // created by its first user
+    DBuf<uint8_t> tmp;
+    StreamCtx() = default;
+    StreamCtx(const StreamCtx &) = delete;
+    StreamCtx &operator=(const StreamCtx &) = delete;
+    ~StreamCtx() {
+        if (st) (void)hipStreamDestroy(st);
+    }
+};
+// One search lane of a handle: two parts of a large batch are searched side by side (the seeding / anchor kernels of one beside
+// the WFA launches of the other), each lane with its share of the scratch budget, its own scratch, streams and rocPRIM storage.
+struct Lane {
+    ScratchArena arena;       // phase buffers of the lane's searches.  First member, so destroyed last: a buffer below that still held a block of it would give it back to a live arena
+    StreamCtx main, producer; // producer: the pseudo-alignment producer of the alignment pipeline
+    Work *work = nullptr;     // device scratch reused across calls (grow-only)
+    AlignCtx *actx[3] = {nullptr, nullptr, nullptr}; // consumer (glue, extend, first WFA passes), pseudo-alignment producer, WFA tail
+};
+
 // Two-pass construction of the packed seed image in HBM (lm_seedpack.hip): every seed is shown twice, in any order and
 // in batches of any size, as (mask, k-mer, value in the reference layout): count() sizes the partitions, place() stores.
 struct SeedPacker {
@@ -470,20 +499,12 @@ struct lm_tune {
 
 struct lm_index {
     lm_tune tune;
-    lm::Work *work = nullptr;       // device scratch reused across calls (grow-only)
-    lm::AlignCtx *actx[3] = {nullptr, nullptr, nullptr}; // consumer (glue, extend, first WFA passes), pseudo-alignment producer, WFA tail
-    // second lane: two parts of a large batch are searched side by side (the seeding / anchor kernels of one beside the
-    // WFA launches of the other), each with half of the scratch budget, its own scratch, streams and rocPRIM storage
-    lm::Work *work1 = nullptr;
-    lm::AlignCtx *actx1[3] = {nullptr, nullptr, nullptr};
-    hipStream_t st_b = nullptr, st2_b = nullptr;
     int active_lanes = 1;
     int budget_lanes = 1; // what BUDGET() divides the scratch budget by (= active_lanes, but 2 in the serialised measurement step of a two-lane search)
     std::mutex mu;                  // one in-flight call per handle
     HostIndex host;
     lm_options opt;
     int device = 0;
-    hipStream_t st = nullptr, st2 = nullptr; // st2: the pseudo-alignment producer of the alignment pipeline
     std::string err;
     // HBM image
     DBuf<uint64_t> d_masks, d_pk_keys, d_pk_vals, d_out_kmers, d_out_vals, d_g_bg;
@@ -513,8 +534,7 @@ struct lm_index {
     }
     // scratch
     LaneSlabs lane_slabs;    // the two fixed slabs the lane arenas work in (LM_ARENA_RESERVE_PCT of the scratch budget)
-    ScratchArena arena[2];   // phase buffers of the searches on this handle, one arena per lane (destroyed after work / actx)
-    DBuf<uint8_t> tmp, tmp2, tmp_b, tmp2_b; // rocPRIM temporary storage (per stream)
+    lm::Lane lane[2];        // lane 0's main stream and storage also serve the loader, the builder and every call outside a search (lm_index_close deletes work / actx first)
     // profiling
     bool prof = false;
     std::mutex prof_mu;
@@ -535,3 +555,16 @@ struct lm_index {
     std::deque<std::string> syn_store;
 };
 
+namespace lm {
+// Binds the calling thread to a lane of `ix` and one of its streams for a scope; the previous binding comes back at the end of
+// the scope, also when an exception leaves it.  Without `with_arena` the thread keeps the arena it had (none, if unbound).
+struct BindScope {
+    const ThreadBind prev = tls_bind;
+    BindScope(lm_index *ix, int lane, StreamCtx &sc, bool with_arena = true) {
+        tls_bind = ThreadBind{lane, sc.st, &sc.tmp, with_arena ? &ix->lane[lane].arena : prev.arena};
+    }
+    BindScope(const BindScope &) = delete;
+    BindScope &operator=(const BindScope &) = delete;
+    ~BindScope() { tls_bind = prev; }
+};
+} // namespace lm

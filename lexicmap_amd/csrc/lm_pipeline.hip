@@ -15,6 +15,7 @@
 #include <cstring>
 #include <map>
 #include <mutex>
+#include <optional>
 #include <sys/stat.h>
 #include <stdexcept>
 #include <tuple>
@@ -43,16 +44,9 @@ thread_local std::string g_open_error;
 namespace lm {
 
 // ---- profiling: HIP events on the library's stream around each named launch ---------------------------------
-// Helpers take the stream and the rocPRIM scratch from here: a host thread may install its own (thread-local) pair to
-// run part of a batch beside the handle's stream; by default it is the handle's.
-static thread_local DBuf<uint8_t> *tls_tmp = nullptr;
-static thread_local int tls_lane = 0; // which of the handle's two lanes this thread works for
-static inline Work *&lane_work(lm_index *ix) { return tls_lane ? ix->work1 : ix->work; }
-static inline AlignCtx **lane_actx(lm_index *ix) { return tls_lane ? ix->actx1 : ix->actx; }
-static inline hipStream_t &lane_st(lm_index *ix) { return tls_lane ? ix->st_b : ix->st; }
-static inline hipStream_t &lane_st2(lm_index *ix) { return tls_lane ? ix->st2_b : ix->st2; }
-static inline DBuf<uint8_t> &lane_tmp(lm_index *ix) { return tls_lane ? ix->tmp_b : ix->tmp; }
-static inline DBuf<uint8_t> &lane_tmp2(lm_index *ix) { return tls_lane ? ix->tmp2_b : ix->tmp2; }
+// Helpers take the stream and the rocPRIM scratch from here: a host thread may bind its own pair (BindScope) to run part of
+// a batch beside the handle's stream; by default it is lane 0's.
+static inline Lane &LANE(lm_index *ix) { return ix->lane[tls_bind.lane]; } // the lane this thread works for
 // the scratch budget of the lane this thread works for
 static inline int64_t BUDGET(lm_index *ix) { return ix->scratch_budget > 0 ? ix->scratch_budget / ix->budget_lanes : ix->scratch_budget; }
 static int device_cus(int device) {
@@ -68,8 +62,8 @@ static double g_dbg_t0 = 0; // LM_DEBUG: start of the running search (time stamp
 static inline void dbg_stamp(const char *what) {
     if (getenv("LM_DEBUG")) fprintf(stderr, "[lm +%.1f ms] %s\n", now_ms() - g_dbg_t0, what);
 }
-static inline hipStream_t S(lm_index *ix) { return tls_stream ? tls_stream : lane_st(ix); }
-static inline DBuf<uint8_t> &TMP(lm_index *ix) { return tls_tmp ? *tls_tmp : lane_tmp(ix); }
+static inline hipStream_t S(lm_index *ix) { return tls_bind.stream ? tls_bind.stream : ix->lane[0].main.st; }
+static inline DBuf<uint8_t> &TMP(lm_index *ix) { return tls_bind.tmp ? *tls_bind.tmp : ix->lane[0].main.tmp; }
 
 struct Prof {
     lm_index *ix;
@@ -1088,7 +1082,7 @@ lm_status lm_index_open_ex(const char *dir, const lm_options *opt, const lm_resi
             return st;
         }
         HIPCHK(hipSetDevice(device));
-        HIPCHK(hipStreamCreate(&ix->st));
+        HIPCHK(hipStreamCreate(&ix->lane[0].main.st));
         HostIndex &h = ix->host;
         // mask prefix table
         int p = h.mask_prefix;
@@ -1453,7 +1447,7 @@ lm_status lm_index_open_ex(const char *dir, const lm_options *opt, const lm_resi
                                                    h.batch_first.size() * 8);
         // the host copy of the packed genomes is no longer needed
         std::vector<uint8_t>().swap(h.gbits);
-        ix->tmp.release();
+        ix->lane[0].main.tmp.release();
         lm_set_scratch_budget(ix);
         if (getenv("LM_DEBUG")) fprintf(stderr, "[lm] loader: done %.0f ms after the genome reader started\n", now_ms() - t_g0);
     } catch (const std::exception &e) {
@@ -1465,19 +1459,13 @@ lm_status lm_index_open_ex(const char *dir, const lm_options *opt, const lm_resi
     return LM_OK;
 }
 
-void lm_free_align_ctx(lm_index *ix, int lane = -1);
+void lm_lane_drop(lm_index *ix, int l); // (Work and AlignCtx are defined further down)
 
 void lm_index_close(lm_index *ix) {
     if (!ix) return;
     prof_resolve(ix);
-    delete ix->work;
-    delete ix->work1;
-    lm_free_align_ctx(ix); // AlignCtx is defined further down
-    if (ix->st) (void)hipStreamDestroy(ix->st);
-    if (ix->st2) (void)hipStreamDestroy(ix->st2);
-    if (ix->st_b) (void)hipStreamDestroy(ix->st_b);
-    if (ix->st2_b) (void)hipStreamDestroy(ix->st2_b);
-    delete ix;
+    for (int l = 0; l < 2; l++) lm_lane_drop(ix, l);
+    delete ix; // per lane: the streams, then their rocPRIM storage, then the arena; the lane slabs after both lanes
 }
 
 lm_status lm_index_get_info(const lm_index *ix, lm_index_info *info) {
@@ -1536,13 +1524,7 @@ void lm_tuning_reload(lm_index *ix) {
     ix->tune = fresh;
     // every variant starts from the same scratch state: both lanes' buffers go back (the lane slabs stay with the handle)
     (void)hipDeviceSynchronize();
-    delete ix->work;
-    ix->work = nullptr;
-    delete ix->work1;
-    ix->work1 = nullptr;
-    lm_free_align_ctx(ix);
-    ix->arena[0].trim();
-    ix->arena[1].trim();
+    for (int l = 0; l < 2; l++) lm_lane_drop(ix, l);
 }
 void lm_profile_reset(lm_index *ix) {
     prof_resolve(ix);
@@ -1756,25 +1738,17 @@ struct AlignCtx {
     // the LDS WFA passes of the four length classes run side by side (a pass ends in a tail of a few long alignments that
     // leaves most CUs idle): each class has its own stream, queue and scratch
     struct LeanCtx {
-        hipStream_t st = nullptr;
         DBuf<int32_t> todo, hdr_pool, arena_pool;
         DBuf<unsigned int> queue;
-        DBuf<uint8_t> tmp;
-        ~LeanCtx() {
-            if (st) (void)hipStreamDestroy(st);
-        }
+        StreamCtx sc; // (last: the stream goes before the buffers its launches used)
     } lean[2 * LM_WFA_CLASSES]; // per length class: the chain that starts at the class's ring width, and the one of the problems predicted wider
     // the global-memory WFA fallback runs beside the LDS passes of the shorter length classes: own stream and buffers
     struct WideCtx {
-        hipStream_t st = nullptr;
         DBuf<WfaIn> in;
         DBuf<WfaOut> out;
         DBuf<int32_t> todo, hdr, arena;
         DBuf<uint64_t> ops;
-        DBuf<uint8_t> tmp;
-        ~WideCtx() {
-            if (st) (void)hipStreamDestroy(st);
-        }
+        StreamCtx sc; // (last, as in LeanCtx)
     } wide;
     AlignCtx() {
         for_each_phase([](auto &b) { b.phase = true; });
@@ -1787,8 +1761,8 @@ struct AlignCtx {
         f(marks); f(msi); f(stack); f(out_n); f(clr_n); f(out); f(out_compact); f(res_off); f(tasks); f(gstage); f(tsrc); f(stage_cmds); f(hsp_in);
         f(hsp_ext); f(ext_cap); f(ext_wcap); f(ext_msi); f(ext_off); f(ext_subs); f(ext_rows); f(ext_rstart);
         f(wfa_in); f(wfa_out);  f(ops_pool);
-        f(wide.in); f(wide.out); f(wide.todo); f(wide.hdr); f(wide.arena); f(wide.ops); f(wide.tmp);
-        for (auto &l : lean) { f(l.todo); f(l.hdr_pool); f(l.arena_pool); f(l.tmp); }
+        f(wide.in); f(wide.out); f(wide.todo); f(wide.hdr); f(wide.arena); f(wide.ops); f(wide.sc.tmp);
+        for (auto &l : lean) { f(l.todo); f(l.hdr_pool); f(l.arena_pool); f(l.sc.tmp); }
     }
     // the alignment half is over: its buffers go back to the handle's scratch arena (the seeding half of the next batch
     // part is carved from the same slabs; both halves sized to their shares of the scratch budget do not fit side by side)
@@ -1809,22 +1783,22 @@ lm_status lm_index_get_residency(const lm_index *ix, lm_residency_info *info) {
     if (!ix || !info) return LM_ERR_ARG;
     *info = ix->res;
     info->stage_bytes = 0;
-    for (AlignCtx *const *set : {ix->actx, ix->actx1})
-        for (int i = 0; i < 3; i++)
-            if (set[i]) info->stage_bytes += (int64_t)set[i]->gstage.bytes();
+    for (const Lane &ln : ix->lane)
+        for (const AlignCtx *c : ln.actx)
+            if (c) info->stage_bytes += (int64_t)c->gstage.bytes();
     return LM_OK;
 }
-void lm_free_align_ctx(lm_index *ix, int lane) { // lane < 0: both
-    if (lane != 1)
-        for (auto &c : ix->actx) {
-            delete c;
-            c = nullptr;
-        }
-    if (lane != 0)
-        for (auto &c : ix->actx1) {
-            delete c;
-            c = nullptr;
-        }
+// lane l's scratch goes back: its buffers to the arena or the device, the arena's empty overflow slabs to the device (the
+// handle's lane slabs and the lane's streams stay)
+void lm_lane_drop(lm_index *ix, int l) {
+    Lane &ln = ix->lane[l];
+    delete ln.work;
+    ln.work = nullptr;
+    for (auto &c : ln.actx) {
+        delete c;
+        c = nullptr;
+    }
+    ln.arena.trim();
 }
 namespace lm {
 
@@ -2139,7 +2113,7 @@ static double div_from_pseudo_pident(double pid) { // table over integer percent
 static void run_wfa(AlignCtx &a, std::vector<WfaIn> &in, std::vector<WfaOut> &out, std::vector<uint64_t> &ops_h,
                     std::vector<int64_t> &ops_off_h, bool want_ops, const std::vector<float> *est_div = nullptr) {
     lm_index *ix = a.ix;
-    const int lane = tls_lane;
+    const int lane = tls_bind.lane;
     int64_t n = (int64_t)in.size();
     out.assign(n, WfaOut());
     ops_off_h.assign(n + 1, 0);
@@ -2414,24 +2388,19 @@ static void run_wfa(AlignCtx &a, std::vector<WfaIn> &in, std::vector<WfaOut> &ou
         wide_thread = std::thread([&, items, level]() {
             try {
                 HIPCHK(hipSetDevice(ix->device));
-                tls_lane = lane;
-                tls_stream = a.wide.st;
-                tls_tmp = &a.wide.tmp;
-                tls_arena = &ix->arena[tls_lane];
+                BindScope bind(ix, lane, a.wide.sc);
                 wide_run(items, level, a.wide);
             } catch (...) {
                 wide_err = std::current_exception();
             }
-            tls_stream = nullptr;
-            tls_tmp = nullptr;
         });
     };
     // the classes side by side, the long ones first (their wavefronts should all be resident from the start); the caller's
     // thread takes the shortest class on its own stream
     // every stream exists before the first thread starts: a failing hipStreamCreate must not unwind past joinable threads
     for (int c = NCH - 1; c >= 1; c--)
-        if (!cls[c].empty() && !a.lean[c].st) HIPCHK(hipStreamCreate(&a.lean[c].st));
-    if (!a.wide.st) HIPCHK(hipStreamCreate(&a.wide.st));
+        if (!cls[c].empty() && !a.lean[c].sc.st) HIPCHK(hipStreamCreate(&a.lean[c].sc.st));
+    if (!a.wide.sc.st) HIPCHK(hipStreamCreate(&a.wide.sc.st));
     std::thread cth[NCH];
     std::exception_ptr cerr[NCH];
     const bool serial = ix->tune.wfa_serial; // exclusive kernel timings: one class after the other
@@ -2444,16 +2413,11 @@ static void run_wfa(AlignCtx &a, std::vector<WfaIn> &in, std::vector<WfaOut> &ou
         cth[c] = std::thread([&, c]() {
             try {
                 HIPCHK(hipSetDevice(ix->device));
-                tls_lane = lane;
-                tls_stream = a.lean[c].st;
-                tls_tmp = &a.lean[c].tmp;
-                tls_arena = &ix->arena[tls_lane];
+                BindScope bind(ix, lane, a.lean[c].sc);
                 class_chain(c);
             } catch (...) {
                 cerr[c] = std::current_exception();
             }
-            tls_stream = nullptr;
-            tls_tmp = nullptr;
         });
         if (serial) cth[c].join();
     }
@@ -2558,13 +2522,13 @@ static void fmt_alignment(const std::vector<uint64_t> &ops, const uint8_t *q, co
 }
 
 static Work &get_work(lm_index *ix, lm_qbatch *qb) {
-    Work *&wk = lane_work(ix);
+    Work *&wk = LANE(ix).work;
     if (!wk) wk = new Work(ix, qb);
     wk->rebind(qb);
     return *wk;
 }
 static AlignCtx &get_actx(lm_index *ix, lm_qbatch *qb, Work *w, lm_stage_stats *st, int slot = 0) {
-    AlignCtx **ac = lane_actx(ix);
+    AlignCtx **ac = LANE(ix).actx;
     if (!ac[slot]) ac[slot] = new AlignCtx();
     AlignCtx &a = *ac[slot];
     a.ix = ix;
@@ -2576,7 +2540,7 @@ static AlignCtx &get_actx(lm_index *ix, lm_qbatch *qb, Work *w, lm_stage_stats *
 
 // The alignment half for tasks [r0, r1) of the batch (whole (query, genome) segments): pseudo-alignment -> glue ->
 // extendMatch -> WFA -> per-genome finalisation, in chunks bounded by the window budget. Appends to `genomes` in task
-// order. Runs on the calling thread's stream (tls_stream) with the private scratch of `a`.
+// order. Runs on the calling thread's stream (S(ix)) with the private scratch of `a`.
 static void align_range(lm_index *ix, lm_qbatch *qb, Work &w, AlignCtx &a, TaskSpan tasks_h, int64_t r0, int64_t r1,
                         lm_stage_stats &st, std::vector<HGenome> &genomes, lm_result *res, std::mutex &strings_mu) {
     // windows of one alignment chunk: the chunk's pseudo-alignment anchors (~0.04 per window base, ~90 B of scratch each)
@@ -2606,16 +2570,15 @@ static void align_range(lm_index *ix, lm_qbatch *qb, Work &w, AlignCtx &a, TaskS
     double ms_pseudo = 0;
     const int64_t total_window = r1 > r0 ? tasks_h[r1 - 1].woff + tasks_h[r1 - 1].wlen - tasks_h[r0].woff : 0;
     const bool pipelined = total_window > max_window_bytes && !ix->tune.no_pipeline;
-    const int lane = tls_lane;
+    const int lane = tls_bind.lane;
     auto producer = [&]() {
         try {
+            std::optional<BindScope> bind; // (not pipelined: this is the caller's thread, which keeps its binding)
             if (pipelined) {
                 HIPCHK(hipSetDevice(ix->device));
-                tls_lane = lane;
-                if (!lane_st2(ix)) HIPCHK(hipStreamCreate(&lane_st2(ix)));
-                tls_stream = lane_st2(ix);
-                tls_tmp = &lane_tmp2(ix);
-                tls_arena = &ix->arena[tls_lane];
+                StreamCtx &sc = ix->lane[lane].producer;
+                if (!sc.st) HIPCHK(hipStreamCreate(&sc.st));
+                bind.emplace(ix, lane, sc);
             }
             int64_t tpos = r0;
             int slot = 0;
@@ -2679,10 +2642,6 @@ static void align_range(lm_index *ix, lm_qbatch *qb, Work &w, AlignCtx &a, TaskS
             }
         } catch (...) {
             prod_err = std::current_exception();
-        }
-        if (pipelined) {
-            tls_stream = nullptr;
-            tls_tmp = nullptr;
         }
         {
             std::lock_guard<std::mutex> l(pm);
@@ -3147,28 +3106,19 @@ static void search_impl(lm_index *ix, lm_qbatch *qb, lm_result *res, const Searc
     double t0 = now_ms(), t1;
     st.query_bases = qb->total_len;
     st.query_kmers = 2 * qb->total_pos;
-    struct TlsScope { // allocations and launches of this thread belong to this handle's arena and stream
-        ScratchArena *pa = tls_arena;
-        hipStream_t ps = tls_stream;
-        explicit TlsScope(lm_index *ix) {
-            tls_arena = &ix->arena[tls_lane];
-            if (!tls_stream) tls_stream = lane_st(ix);
-        }
-        ~TlsScope() {
-            tls_arena = pa;
-            tls_stream = ps;
-        }
-    } tls_scope(ix);
+    // allocations and launches of this thread belong to its lane's arena and main stream (on the caller's thread of a plain
+    // batch: lane 0's; on a lane's thread, whose binding has no arena: the same stream again, now with the arena)
+    BindScope bind(ix, tls_bind.lane, LANE(ix).main);
     g_dbg_t0 = now_ms();
     dbg_stamp("search of a batch part starts");
     if (BUDGET(ix) > 0) { // scratch of the previous part's alignment half (the halves alternate)
         HIPCHK(hipStreamSynchronize(S(ix))); // (every worker thread of the previous part synchronised its stream and was joined)
         int64_t freed = 0;
         for (int j = 0; j < 3; j++)
-            if (AlignCtx *c = lane_actx(ix)[j]) freed += c->release_big(BUDGET(ix) / 200);
+            if (AlignCtx *c = LANE(ix).actx[j]) freed += c->release_big(BUDGET(ix) / 200);
         if (freed > 0 && getenv("LM_DEBUG"))
             fprintf(stderr, "[lm] alignment scratch of the previous part released: %.2f GB (arena: %.2f GB in slabs, %lld slab allocations so far)\n",
-                    (double)freed / 1e9, (double)ix->arena[tls_lane].slab_bytes / 1e9, (long long)ix->arena[tls_lane].slab_allocs);
+                    (double)freed / 1e9, (double)LANE(ix).arena.slab_bytes / 1e9, (long long)LANE(ix).arena.slab_allocs);
     }
     dbg_stamp("previous alignment scratch released");
     Work &w = get_work(ix, qb);
@@ -3508,16 +3458,27 @@ static std::pair<lm_qbatch *, lm_qbatch *> halve_qbatch(lm_index *ix, lm_qbatch 
 
 extern "C" {
 
-// the scratch of the lane this thread works for goes back to the device (after an allocation failure)
-static void drop_scratch(lm_index *ix, const char *why) {
+// the scratch of lane l goes back to the device (after an allocation failure), its rocPRIM storage included
+static void drop_scratch(lm_index *ix, int l, const char *why) {
     (void)hipDeviceSynchronize();
-    delete lane_work(ix);
-    lane_work(ix) = nullptr;
-    lm_free_align_ctx(ix, tls_lane);
-    lane_tmp(ix).release();
-    lane_tmp2(ix).release();
-    ix->arena[tls_lane].trim(); // (its overflow slabs; the handle's lane slabs stay)
-    if (getenv("LM_DEBUG")) fprintf(stderr, "[lm] device scratch of lane %d dropped after: %s\n", tls_lane, why);
+    lm_lane_drop(ix, l);
+    ix->lane[l].main.tmp.release();
+    ix->lane[l].producer.tmp.release();
+    if (getenv("LM_DEBUG")) fprintf(stderr, "[lm] device scratch of lane %d dropped after: %s\n", l, why);
+}
+// what an aborted attempt left in a result (rows, CIGAR / alignment strings) must not outlive it
+static void clear_result(lm_result *res) {
+    for (auto *str : res->strings) delete str;
+    res->strings.clear();
+    res->rows.clear();
+    res->stats = lm_stage_stats();
+}
+// the pieces that take the place of a part whose search was aborted: cut by how far its seed anchors were over the budget
+// (PartTooLarge), or two halves (over == 0: an allocation failed)
+static std::vector<lm_qbatch *> part_pieces(lm_index *ix, lm_qbatch *part, double over) {
+    if (over > 0) return split_qbatch(ix, part, over);
+    auto ab = halve_qbatch(ix, part);
+    return {ab.first, ab.second};
 }
 // All parts of the caller's batch, results in order.  A part whose seed anchors outgrow the device (or whose scratch
 // allocation fails) is halved in place; the split stays in the batch handle, so the next search of the same resident batch
@@ -3527,12 +3488,11 @@ static void drop_scratch(lm_index *ix, const char *why) {
 static void search_parts(lm_index *ix, lm_qbatch *qb, lm_result *res, const SearchCtl *ctl) {
     std::lock_guard<std::mutex> lock(ix->mu); // one in-flight call per handle
     HIPCHK(hipSetDevice(ix->device));
-    tls_lane = 0;
     ix->active_lanes = 1;
     ix->budget_lanes = 1;
     lm_reserve_lane_slabs(ix); // once per handle (LaneSlabs, lm_internal.h); a production-size index did it when it was opened
     if (qb->parts.empty()) {
-        ix->lane_slabs.assign(ix->arena[0], ix->arena[1], 1); // (false: a block is live - the assignment stays, overflow slabs serve)
+        ix->lane_slabs.assign(ix->lane[0].arena, ix->lane[1].arena, 1); // (false: a block is live - the assignment stays, overflow slabs serve)
         double over = 0;
         try {
             search_impl(ix, qb, res, ctl);
@@ -3541,19 +3501,10 @@ static void search_parts(lm_index *ix, lm_qbatch *qb, lm_result *res, const Sear
             over = e.over;
         } catch (const DeviceOOM &e) { // the shares of the scratch budget are estimates: retry on half the queries
             if (qb->nq < 2) throw;
-            drop_scratch(ix, e.what());
+            drop_scratch(ix, 0, e.what());
         }
-        // what the aborted attempt left in the caller's result (rows, CIGAR / alignment strings) must not outlive it
-        for (auto *str : res->strings) delete str;
-        res->strings.clear();
-        res->rows.clear();
-        res->stats = lm_stage_stats();
-        if (over > 0) {
-            qb->parts = split_qbatch(ix, qb, over);
-        } else {
-            auto ab = halve_qbatch(ix, qb);
-            qb->parts = {ab.first, ab.second};
-        }
+        clear_result(res);
+        qb->parts = part_pieces(ix, qb, over);
         qb->d_seq.release(); // the plain batch's own device copy is no longer used
         qb->d_qoff.release();
         qb->d_posoff.release();
@@ -3581,23 +3532,17 @@ static void search_parts(lm_index *ix, lm_qbatch *qb, lm_result *res, const Sear
     const int lanes = (blanes == 2 && !ix->tune.wfa_serial) ? 2 : 1;
     ix->active_lanes = lanes;
     ix->budget_lanes = blanes;
-    if (!ix->lane_slabs.assign(ix->arena[0], ix->arena[1], blanes)) { // a block outlived the previous search: give everything back first
-        for (int l = 0; l < 2; l++) {
-            tls_lane = l;
-            drop_scratch(ix, "lane slabs change hands");
-        }
-        tls_lane = 0;
-        ix->lane_slabs.assign(ix->arena[0], ix->arena[1], blanes);
+    if (!ix->lane_slabs.assign(ix->lane[0].arena, ix->lane[1].arena, blanes)) { // a block outlived the previous search: give everything back first
+        for (int l = 0; l < 2; l++) drop_scratch(ix, l, "lane slabs change hands");
+        ix->lane_slabs.assign(ix->lane[0].arena, ix->lane[1].arena, blanes);
     }
     auto lane_fn = [&](int lane) {
-        tls_lane = lane;
-        hipStream_t saved_stream = tls_stream;
-        DBuf<uint8_t> *saved_tmp = tls_tmp;
         try {
             HIPCHK(hipSetDevice(ix->device));
-            if (!lane_st(ix)) HIPCHK(hipStreamCreate(&lane_st(ix)));
-            tls_stream = lane_st(ix);
-            tls_tmp = &lane_tmp(ix);
+            StreamCtx &sc = ix->lane[lane].main;
+            if (!sc.st) HIPCHK(hipStreamCreate(&sc.st));
+            // (no arena here: the re-split and upload of a halved part allocate as the caller's thread does; search_impl binds it)
+            BindScope bind(ix, lane, sc, false);
             while (true) {
                 std::list<PartState>::iterator it;
                 {
@@ -3619,24 +3564,16 @@ static void search_parts(lm_index *ix, lm_qbatch *qb, lm_result *res, const Sear
                 } catch (const DeviceOOM &e) {
                     if (it->part->nq < 2) throw;
                     if (getenv("LM_DEBUG_MEM")) fprintf(stderr, "[lm] lane %d: a part of %d queries is halved after: %s\n", lane, it->part->nq, e.what());
-                    drop_scratch(ix, e.what());
+                    drop_scratch(ix, lane, e.what());
                     split = true;
                 }
                 if (split) {
-                    std::vector<lm_qbatch *> pieces;
-                    if (over > 0) {
-                        pieces = split_qbatch(ix, it->part, over);
-                    } else {
-                        auto ab = halve_qbatch(ix, it->part);
-                        pieces = {ab.first, ab.second};
-                    }
+                    const std::vector<lm_qbatch *> pieces = part_pieces(ix, it->part, over);
                     std::lock_guard<std::mutex> l(lm_);
                     delete it->part;
                     it->part = pieces[0]; // this entry becomes the first piece, the others follow it in order
                     it->state = 0;
-                    for (auto *str : it->res.strings) delete str;
-                    it->res.strings.clear();
-                    it->res.rows.clear();
+                    clear_result(&it->res);
                     auto nx = std::next(it);
                     for (size_t pi = 1; pi < pieces.size(); pi++) {
                         auto ins = todo.emplace(nx);
@@ -3652,9 +3589,6 @@ static void search_parts(lm_index *ix, lm_qbatch *qb, lm_result *res, const Sear
             std::lock_guard<std::mutex> l(lm_);
             if (!err) err = std::current_exception();
         }
-        tls_stream = saved_stream;
-        tls_tmp = saved_tmp;
-        tls_lane = 0;
     };
     std::thread second;
     if (lanes == 2) second = std::thread(lane_fn, 1);
@@ -3664,8 +3598,8 @@ static void search_parts(lm_index *ix, lm_qbatch *qb, lm_result *res, const Sear
         size_t fr = 0, tot = 0;
         (void)hipMemGetInfo(&fr, &tot);
         fprintf(stderr, "[lm] scratch after a search of %zu parts on %d lane(s) (budget / %d): lane slabs %.2f GB; overflow slabs: lane 0 %.2f GB (%lld device allocations so far), lane 1 %.2f GB (%lld); device free %.2f GB; all buffers of this library %.2f GB\n",
-                todo.size(), lanes, blanes, (double)ix->lane_slabs.bytes() / 1e9, (double)ix->arena[0].slab_bytes / 1e9, (long long)ix->arena[0].slab_allocs,
-                (double)ix->arena[1].slab_bytes / 1e9, (long long)ix->arena[1].slab_allocs, (double)fr / 1e9, (double)g_dbuf_bytes.load() / 1e9);
+                todo.size(), lanes, blanes, (double)ix->lane_slabs.bytes() / 1e9, (double)ix->lane[0].arena.slab_bytes / 1e9, (long long)ix->lane[0].arena.slab_allocs,
+                (double)ix->lane[1].arena.slab_bytes / 1e9, (long long)ix->lane[1].arena.slab_allocs, (double)fr / 1e9, (double)g_dbuf_bytes.load() / 1e9);
     }
     ix->active_lanes = 1;
     ix->budget_lanes = 1;
@@ -4186,14 +4120,14 @@ void lm_scratch_session_end(lm_index *ix) {
 void *lm_scratch_borrow(lm_index *ix, size_t bytes) {
     if (!ix || bytes == 0) return nullptr;
     try {
-        return ix->arena[0].alloc(bytes);
+        return ix->lane[0].arena.alloc(bytes);
     } catch (const std::exception &e) {
         ix->err = e.what();
         return nullptr;
     }
 }
 void lm_scratch_return(lm_index *ix, void *p) {
-    if (ix && p) (void)ix->arena[0].release(p);
+    if (ix && p) (void)ix->lane[0].arena.release(p);
 }
 void lm_attach_names(lm_index *ix, lm_hsp *rows, size_t n) {
     if (!ix || n == 0) return;

@@ -454,53 +454,55 @@ void SeedPacker::begin(lm_index *ix_, int64_t local_genomes, int64_t max_genome_
     if (pos_bits > 28) throw HipError("seed image: genome longer than 2^28 bases (lib-index-build.go:421-425)");
     if (gid_bits + pos_bits + 1 > 64) throw HipError("seed image: value does not fit 64 bits");
     const int64_t nmd = 2ll * h.M;
-    ix->d_part_tab.alloc_exact((size_t)(nmd * P1), true, ix->st);
-    out_cnt.alloc_exact((size_t)nmd + 1, true, ix->st);
+    ix->d_part_tab.alloc_exact((size_t)(nmd * P1), true, ix->lane[0].main.st);
+    out_cnt.alloc_exact((size_t)nmd + 1, true, ix->lane[0].main.st);
     n_main = n_out = 0;
     placing = false;
 }
 
 void SeedPacker::count(const uint16_t *mask, const uint64_t *kmer, const uint64_t *val, int64_t n) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(k_sp_count, dim3(sp_grid(n)), dim3(256), 0, ix->st, sp_params(*this), mask, kmer, val, n,
+    hipLaunchKernelGGL(k_sp_count, dim3(sp_grid(n)), dim3(256), 0, ix->lane[0].main.st, sp_params(*this), mask, kmer, val, n,
                        ix->d_part_tab.p, out_cnt.p);
 }
 
 void SeedPacker::end_count() {
+    const hipStream_t st = ix->lane[0].main.st;
     const int64_t nmd = 2ll * ix->host.M;
     DBuf<unsigned long long> md_cnt;
-    md_cnt.alloc_exact((size_t)nmd + 1, true, ix->st);
-    hipLaunchKernelGGL(k_sp_scan_rows, dim3((unsigned)std::min<int64_t>(nmd, 65536)), dim3(256), 0, ix->st, ix->d_part_tab.p,
+    md_cnt.alloc_exact((size_t)nmd + 1, true, st);
+    hipLaunchKernelGGL(k_sp_scan_rows, dim3((unsigned)std::min<int64_t>(nmd, 65536)), dim3(256), 0, st, ix->d_part_tab.p,
                        P1, nmd, md_cnt.p);
     ix->d_md_off.alloc_exact((size_t)nmd + 1);
     ix->d_out_off.alloc_exact((size_t)nmd + 1);
-    prim_scan_to_i64(ix->st, ix->tmp, md_cnt.p, (size_t)nmd, ix->d_md_off.p);
-    prim_scan_to_i64(ix->st, ix->tmp, out_cnt.p, (size_t)nmd, ix->d_out_off.p);
+    prim_scan_to_i64(st, ix->lane[0].main.tmp, md_cnt.p, (size_t)nmd, ix->d_md_off.p);
+    prim_scan_to_i64(st, ix->lane[0].main.tmp, out_cnt.p, (size_t)nmd, ix->d_out_off.p);
     int64_t tot[2];
-    HIPCHK(hipMemcpyAsync(&tot[0], ix->d_md_off.p + nmd, sizeof(int64_t), hipMemcpyDeviceToHost, ix->st));
-    HIPCHK(hipMemcpyAsync(&tot[1], ix->d_out_off.p + nmd, sizeof(int64_t), hipMemcpyDeviceToHost, ix->st));
-    HIPCHK(hipStreamSynchronize(ix->st));
+    HIPCHK(hipMemcpyAsync(&tot[0], ix->d_md_off.p + nmd, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&tot[1], ix->d_out_off.p + nmd, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     n_main = tot[0];
     n_out = tot[1];
     const int val_bits = gid_bits + pos_bits + 1;
     // +2 words: lm_bits_get may touch the word after the last element
-    ix->d_pk_keys.alloc_exact((size_t)((n_main * key_bits + 63) / 64 + 2), true, ix->st);
-    ix->d_pk_vals.alloc_exact((size_t)((n_main * val_bits + 63) / 64 + 2), true, ix->st);
+    ix->d_pk_keys.alloc_exact((size_t)((n_main * key_bits + 63) / 64 + 2), true, st);
+    ix->d_pk_vals.alloc_exact((size_t)((n_main * val_bits + 63) / 64 + 2), true, st);
     ix->d_out_kmers.alloc_exact((size_t)n_out + 1);
     ix->d_out_vals.alloc_exact((size_t)n_out + 1);
-    HIPCHK(hipMemsetAsync(out_cnt.p, 0, ((size_t)nmd + 1) * sizeof(unsigned long long), ix->st)); // now the outlier cursors
+    HIPCHK(hipMemsetAsync(out_cnt.p, 0, ((size_t)nmd + 1) * sizeof(unsigned long long), st)); // now the outlier cursors
     placing = true;
 }
 
 void SeedPacker::place(const uint16_t *mask, const uint64_t *kmer, const uint64_t *val, int64_t n) {
     if (n <= 0) return;
     if (!placing) throw HipError("SeedPacker::place before end_count");
-    hipLaunchKernelGGL(k_sp_place, dim3(sp_grid(n)), dim3(256), 0, ix->st, sp_params(*this), mask, kmer, val, n,
+    hipLaunchKernelGGL(k_sp_place, dim3(sp_grid(n)), dim3(256), 0, ix->lane[0].main.st, sp_params(*this), mask, kmer, val, n,
                        ix->d_part_tab.p, ix->d_md_off.p, ix->d_pk_keys.p, ix->d_pk_vals.p, ix->d_out_off.p, out_cnt.p,
                        ix->d_out_kmers.p, ix->d_out_vals.p);
 }
 
 void SeedPacker::finish() {
+    const hipStream_t st = ix->lane[0].main.st;
     const HostIndex &h = ix->host;
     const int64_t nmd = 2ll * h.M;
     const int val_bits = gid_bits + pos_bits + 1;
@@ -510,17 +512,17 @@ void SeedPacker::finish() {
     const unsigned long long big_cap = (unsigned long long)(n_main / SP_MAXN) + 1024;
     DBuf<unsigned long long> big, nbig;
     big.alloc_exact(big_cap);
-    nbig.alloc_exact(1, true, ix->st);
+    nbig.alloc_exact(1, true, st);
     if (n_main > 0) {
         const int64_t nparts = nmd * (P1 - 1);
         const int dbg_mode = 0; // (the kernel's timing-experiment modes are not reachable any more)
         const double t0 = now_ms();
-        hipLaunchKernelGGL(k_sp_sort_parts, dim3((unsigned)std::min<int64_t>(nparts, (int64_t)1 << 22)), dim3(64), 0, ix->st,
+        hipLaunchKernelGGL(k_sp_sort_parts, dim3((unsigned)std::min<int64_t>(nparts, (int64_t)1 << 22)), dim3(64), 0, st,
                            ix->d_part_tab.p, ix->d_md_off.p, P1, nmd, key_bits, val_bits, ix->d_pk_keys.p, ix->d_pk_vals.p,
                            big.p, big_cap, nbig.p, dbg_mode);
         unsigned long long nb = 0;
-        HIPCHK(hipMemcpyAsync(&nb, nbig.p, sizeof nb, hipMemcpyDeviceToHost, ix->st));
-        HIPCHK(hipStreamSynchronize(ix->st));
+        HIPCHK(hipMemcpyAsync(&nb, nbig.p, sizeof nb, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
         if (getenv("LM_DEBUG"))
             fprintf(stderr, "[lm] seed image: partition sort kernel %.0f ms (mode %d), %llu partitions above %d seeds\n", now_ms() - t0,
                     dbg_mode, nb, SP_MAXN);
@@ -529,14 +531,14 @@ void SeedPacker::finish() {
             const double t1 = now_ms();
             DBuf<int64_t> bfirst, bcnt, boff;
             bfirst.alloc_exact((size_t)nb + 1);
-            bcnt.alloc_exact((size_t)nb + 1, true, ix->st);
+            bcnt.alloc_exact((size_t)nb + 1, true, st);
             boff.alloc_exact((size_t)nb + 2);
-            hipLaunchKernelGGL(k_sp_big_info, dim3(sp_grid((int64_t)nb)), dim3(256), 0, ix->st, big.p, (int64_t)nb, ix->d_part_tab.p,
+            hipLaunchKernelGGL(k_sp_big_info, dim3(sp_grid((int64_t)nb)), dim3(256), 0, st, big.p, (int64_t)nb, ix->d_part_tab.p,
                                ix->d_md_off.p, P1, bfirst.p, bcnt.p);
-            prim_scan_to_i64(ix->st, ix->tmp, bcnt.p, (size_t)nb, boff.p);
+            prim_scan_to_i64(st, ix->lane[0].main.tmp, bcnt.p, (size_t)nb, boff.p);
             std::vector<int64_t> off((size_t)nb + 1);
-            HIPCHK(hipMemcpyAsync(off.data(), boff.p, ((size_t)nb + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ix->st));
-            HIPCHK(hipStreamSynchronize(ix->st));
+            HIPCHK(hipMemcpyAsync(off.data(), boff.p, ((size_t)nb + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
             // batches of whole partitions: 4 temporary u64 arrays, at most a quarter of what is free and 2^31 elements
             size_t fr = 0, tot = 0;
             (void)hipMemGetInfo(&fr, &tot);
@@ -554,13 +556,13 @@ void SeedPacker::finish() {
                 v0.ensure((size_t)E);
                 v1.ensure((size_t)E);
                 rel.ensure((size_t)nseg + 1);
-                hipLaunchKernelGGL(k_sp_unpack_many, dim3(sp_grid(E)), dim3(256), 0, ix->st, ix->d_pk_keys.p, ix->d_pk_vals.p, key_bits,
+                hipLaunchKernelGGL(k_sp_unpack_many, dim3(sp_grid(E)), dim3(256), 0, st, ix->d_pk_keys.p, ix->d_pk_vals.p, key_bits,
                                    val_bits, bfirst.p + b0, boff.p + b0, nseg, off[b0], E, k0.p, v0.p);
-                hipLaunchKernelGGL(k_sp_rel_offsets, dim3(sp_grid(nseg + 1)), dim3(256), 0, ix->st, boff.p + b0, nseg, off[b0], rel.p);
-                prim_segmented_sort_pairs(ix->st, ix->tmp, k0.p, k1.p, v0.p, v1.p, (size_t)E, (size_t)nseg, rel.p, 0, key_bits);
-                hipLaunchKernelGGL(k_sp_repack_many, dim3((unsigned)std::min<int64_t>(nseg, 65536)), dim3(256), 0, ix->st,
+                hipLaunchKernelGGL(k_sp_rel_offsets, dim3(sp_grid(nseg + 1)), dim3(256), 0, st, boff.p + b0, nseg, off[b0], rel.p);
+                prim_segmented_sort_pairs(st, ix->lane[0].main.tmp, k0.p, k1.p, v0.p, v1.p, (size_t)E, (size_t)nseg, rel.p, 0, key_bits);
+                hipLaunchKernelGGL(k_sp_repack_many, dim3((unsigned)std::min<int64_t>(nseg, 65536)), dim3(256), 0, st,
                                    ix->d_pk_keys.p, ix->d_pk_vals.p, key_bits, val_bits, bfirst.p + b0, rel.p, nseg, k1.p, v1.p);
-                HIPCHK(hipStreamSynchronize(ix->st));
+                HIPCHK(hipStreamSynchronize(st));
                 done_elems += E;
                 b0 = b1;
             }
@@ -574,15 +576,15 @@ void SeedPacker::finish() {
         DBuf<uint64_t> k1, v1;
         k1.alloc_exact((size_t)n_out + 1);
         v1.alloc_exact((size_t)n_out + 1);
-        prim_segmented_sort_pairs(ix->st, ix->tmp, ix->d_out_kmers.p, k1.p, ix->d_out_vals.p, v1.p, (size_t)n_out, (size_t)nmd,
+        prim_segmented_sort_pairs(st, ix->lane[0].main.tmp, ix->d_out_kmers.p, k1.p, ix->d_out_vals.p, v1.p, (size_t)n_out, (size_t)nmd,
                                   ix->d_out_off.p, 0, 2 * h.k);
-        HIPCHK(hipStreamSynchronize(ix->st));
+        HIPCHK(hipStreamSynchronize(st));
         std::swap(ix->d_out_kmers.p, k1.p);
         std::swap(ix->d_out_kmers.cap, k1.cap);
         std::swap(ix->d_out_vals.p, v1.p);
         std::swap(ix->d_out_vals.cap, v1.cap);
     }
-    HIPCHK(hipStreamSynchronize(ix->st));
+    HIPCHK(hipStreamSynchronize(st));
     out_cnt.release();
     DevIndexView &v = ix->view;
     v.part_bases = a;
@@ -632,11 +634,11 @@ extern "C" lm_status lm_index_mask_seeds(lm_index *ix, int32_t mask, uint64_t *k
             if (nm > 0) {
                 dk.ensure((size_t)nm);
                 dv.ensure((size_t)nm);
-                hipLaunchKernelGGL(lm::k_sp_dump_list, dim3(lm::sp_grid(nm)), dim3(256), 0, ix->st, ix->view,
+                hipLaunchKernelGGL(lm::k_sp_dump_list, dim3(lm::sp_grid(nm)), dim3(256), 0, ix->lane[0].main.st, ix->view,
                                    (uint32_t)(2 * mask + dir), nm, dk.p, dv.p);
-                HIPCHK(hipMemcpyAsync(kmers + w, dk.p, (size_t)nm * 8, hipMemcpyDeviceToHost, ix->st));
-                HIPCHK(hipMemcpyAsync(vals + w, dv.p, (size_t)nm * 8, hipMemcpyDeviceToHost, ix->st));
-                HIPCHK(hipStreamSynchronize(ix->st));
+                HIPCHK(hipMemcpyAsync(kmers + w, dk.p, (size_t)nm * 8, hipMemcpyDeviceToHost, ix->lane[0].main.st));
+                HIPCHK(hipMemcpyAsync(vals + w, dv.p, (size_t)nm * 8, hipMemcpyDeviceToHost, ix->lane[0].main.st));
+                HIPCHK(hipStreamSynchronize(ix->lane[0].main.st));
                 w += (size_t)nm;
             }
             if (no > 0) {
@@ -852,10 +854,11 @@ struct SeedLists {
 
 template <typename T> static void sp_upload(lm_index *ix, DBuf<T> &d, const std::vector<T> &v) {
     d.alloc_exact(std::max<size_t>(v.size(), 1));
-    if (!v.empty()) HIPCHK(hipMemcpyAsync(d.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, ix->st));
+    if (!v.empty()) HIPCHK(hipMemcpyAsync(d.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, ix->lane[0].main.st));
 }
 
 static void seed_lists(lm_index *ix, const char *who, const uint64_t *keys, size_t nkeys, SeedLists &L) {
+    const hipStream_t st = ix->lane[0].main.st;
     const HostIndex &h = ix->host;
     const int64_t nlocal = (int64_t)h.genomes.size();
     const int M = h.M;
@@ -900,9 +903,9 @@ static void seed_lists(lm_index *ix, const char *who, const uint64_t *keys, size
     }
     // ---- the forward lists numbered back to back
     std::vector<int64_t> md_off((size_t)2 * M + 1), out_off((size_t)2 * M + 1), foff[2];
-    HIPCHK(hipMemcpyAsync(md_off.data(), ix->d_md_off.p, md_off.size() * 8, hipMemcpyDeviceToHost, ix->st));
-    HIPCHK(hipMemcpyAsync(out_off.data(), ix->d_out_off.p, out_off.size() * 8, hipMemcpyDeviceToHost, ix->st));
-    HIPCHK(hipStreamSynchronize(ix->st));
+    HIPCHK(hipMemcpyAsync(md_off.data(), ix->d_md_off.p, md_off.size() * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(out_off.data(), ix->d_out_off.p, out_off.size() * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     for (int f = 0; f < 2; f++) {
         const std::vector<int64_t> &o = f ? out_off : md_off;
         foff[f].assign((size_t)M + 1, 0);
@@ -918,7 +921,7 @@ static void seed_lists(lm_index *ix, const char *who, const uint64_t *keys, size
     sp_upload(ix, d_oslot, oslot);
     sp_upload(ix, d_foff[0], foff[0]);
     sp_upload(ix, d_foff[1], foff[1]);
-    d_cnt.alloc_exact(1, true, ix->st);
+    d_cnt.alloc_exact(1, true, st);
     const SeedSelDev sel{d_slot.p, nlocal, d_okeys.p, d_oslot.p, nsel};
     // pieces: at most 2^26 seeds per launch as for lm_index_builder_extend; tests make them small (no result depends on it)
     int64_t piece = (int64_t)1 << 26;
@@ -931,7 +934,7 @@ static void seed_lists(lm_index *ix, const char *who, const uint64_t *keys, size
                 int64_t l0, l1;
                 sw_piece_lists(foff[f].data(), M, s0, s1, &l0, &l1);
                 const unsigned grid = (unsigned)std::min<int64_t>((s1 - s0 + 255) / 256, 2048); // at most 8 workgroups per CU, then a grid stride
-#define SP_LOCS_LAUNCH(F, C) hipLaunchKernelGGL((k_sp_seed_locs<F, C>), dim3(grid), dim3(256), 0, ix->st, ix->view, d_foff[f].p, l0, l1, s0, s1, sel, out, cap, d_cnt.p)
+#define SP_LOCS_LAUNCH(F, C) hipLaunchKernelGGL((k_sp_seed_locs<F, C>), dim3(grid), dim3(256), 0, st, ix->view, d_foff[f].p, l0, l1, s0, s1, sel, out, cap, d_cnt.p)
                 if (f) {
                     if (count) SP_LOCS_LAUNCH(true, true);
                     else SP_LOCS_LAUNCH(true, false);
@@ -944,8 +947,8 @@ static void seed_lists(lm_index *ix, const char *who, const uint64_t *keys, size
             }
         HIPCHK(hipGetLastError());
         unsigned long long c = 0;
-        HIPCHK(hipMemcpyAsync(&c, d_cnt.p, sizeof c, hipMemcpyDeviceToHost, ix->st));
-        HIPCHK(hipStreamSynchronize(ix->st));
+        HIPCHK(hipMemcpyAsync(&c, d_cnt.p, sizeof c, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
         return (int64_t)c;
     };
     // ---- the size of the key array: every forward seed when every record is wanted, else a counting pass
@@ -953,7 +956,7 @@ static void seed_lists(lm_index *ix, const char *who, const uint64_t *keys, size
     int64_t n = nsel > 0 ? nfwd[0] + nfwd[1] : 0; // (keys given, nkeys = 0: no record, no seed, nothing is walked)
     if (!all && nsel > 0) {
         n = walk(true, nullptr, 0);
-        HIPCHK(hipMemsetAsync(d_cnt.p, 0, sizeof(unsigned long long), ix->st));
+        HIPCHK(hipMemsetAsync(d_cnt.p, 0, sizeof(unsigned long long), st));
     }
     const double t1 = now_ms();
     try {
@@ -971,15 +974,15 @@ static void seed_lists(lm_index *ix, const char *who, const uint64_t *keys, size
     if (got != n) throw HipError(std::string(who) + ": the image holds " + std::to_string(got) + " forward seeds of the selection where " + std::to_string(n) + " were counted");
     const double t2 = now_ms();
     try {
-        prim_sort_keys(ix->st, ix->tmp, L.ent2.p, L.ent.p, (size_t)n, 0, 32 + bits_for(std::max<int64_t>(nsel, 2)));
+        prim_sort_keys(st, ix->lane[0].main.tmp, L.ent2.p, L.ent.p, (size_t)n, 0, 32 + bits_for(std::max<int64_t>(nsel, 2)));
     } catch (const DeviceOOM &e) {
         throw DeviceOOM(std::string(who) + ": the radix sort of " + std::to_string(n) + " keys needs scratch beside its two key arrays: " + e.what());
     }
-    if (dbg) HIPCHK(hipStreamSynchronize(ix->st));
+    if (dbg) HIPCHK(hipStreamSynchronize(st));
     const double t3 = now_ms();
-    hipLaunchKernelGGL(k_sp_seed_segment, dim3(sp_grid(n + 1)), dim3(256), 0, ix->st, L.ent.p, n, nsel, L.off.p, L.locs.p);
+    hipLaunchKernelGGL(k_sp_seed_segment, dim3(sp_grid(n + 1)), dim3(256), 0, st, L.ent.p, n, nsel, L.off.p, L.locs.p);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(ix->st));
+    HIPCHK(hipStreamSynchronize(st));
     L.ent2.release(); // (the unsorted keys: the distance pass allocates its rows in their place)
     L.n = n;
     if (dbg) {
@@ -1031,15 +1034,16 @@ extern "C" lm_status lm_index_seed_positions(lm_index *ix, const uint64_t *keys,
     if (!ix || !out) return LM_ERR_ARG;
     *out = nullptr;
     std::unique_ptr<lm_seedpos> res(new lm_seedpos());
+    const hipStream_t stream = ix->lane[0].main.st;
     const lm_status st = seed_call(ix, [&]() {
         lm::SeedLists L;
         lm::seed_lists(ix, "lm_index_seed_positions", keys, nkeys, L);
         res->keys = L.keys;
         res->off.resize(L.keys.size() + 1);
         res->locs.resize((size_t)L.n);
-        HIPCHK(hipMemcpyAsync(res->off.data(), L.off.p, res->off.size() * 8, hipMemcpyDeviceToHost, ix->st));
-        if (L.n > 0) HIPCHK(hipMemcpyAsync(res->locs.data(), L.locs.p, (size_t)L.n * 4, hipMemcpyDeviceToHost, ix->st));
-        HIPCHK(hipStreamSynchronize(ix->st));
+        HIPCHK(hipMemcpyAsync(res->off.data(), L.off.p, res->off.size() * 8, hipMemcpyDeviceToHost, stream));
+        if (L.n > 0) HIPCHK(hipMemcpyAsync(res->locs.data(), L.locs.p, (size_t)L.n * 4, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
     });
     if (st == LM_OK) *out = res.release();
     return st;
@@ -1060,6 +1064,7 @@ extern "C" lm_status lm_index_seed_distances(lm_index *ix, const uint64_t *keys,
     lm_seed_dist_opt opt = {0, 0, 0, 0};
     if (opt_in) opt = *opt_in;
     std::unique_ptr<lm_seed_dist> res(new lm_seed_dist());
+    const hipStream_t stream = ix->lane[0].main.st;
     const lm_status st = seed_call(ix, [&]() {
         if (opt.hist_bins > 0 && opt.hist_width < 1) throw SeedArg("lm_index_seed_distances: hist_bins = " + std::to_string(opt.hist_bins) + " with hist_width < 1");
         if (opt.hist_bins > 4096) throw SeedArg("lm_index_seed_distances: hist_bins = " + std::to_string(opt.hist_bins) + " (at most 4096 counters)");
@@ -1089,24 +1094,24 @@ extern "C" lm_status lm_index_seed_distances(lm_index *ix, const uint64_t *keys,
         sp_upload(ix, d_coff, coff);
         sp_upload(ix, d_cstart, cstart);
         sp_upload(ix, d_keys, L.keys);
-        d_seeded.alloc_exact((size_t)nsel, true, ix->st);
-        d_max.alloc_exact((size_t)nsel, true, ix->st);
-        d_hist.alloc_exact(std::max<size_t>(opt.hist_bins, 1), true, ix->st);
-        d_tile_cnt.alloc_exact((size_t)ntiles + 1, true, ix->st);
-        d_tile_off.alloc_exact((size_t)ntiles + 1, true, ix->st);
+        d_seeded.alloc_exact((size_t)nsel, true, stream);
+        d_max.alloc_exact((size_t)nsel, true, stream);
+        d_hist.alloc_exact(std::max<size_t>(opt.hist_bins, 1), true, stream);
+        d_tile_cnt.alloc_exact((size_t)ntiles + 1, true, stream);
+        d_tile_off.alloc_exact((size_t)ntiles + 1, true, stream);
         d_recs.alloc_exact((size_t)nsel);
         SdArgs a{L.ent.p, n, ntiles, d_coff.p, d_cstart.p, opt.min_dist, opt.hist_bins, opt.hist_width, d_max.p, d_seeded.p, d_hist.p,
                  d_tile_cnt.p, d_tile_off.p, nullptr};
         const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ntiles, 2048));
         int64_t nrows = 0;
         if (n > 0) {
-            hipLaunchKernelGGL(k_sd_pass<false>, dim3(grid), dim3(256), (size_t)opt.hist_bins * 4, ix->st, a);
+            hipLaunchKernelGGL(k_sd_pass<false>, dim3(grid), dim3(256), (size_t)opt.hist_bins * 4, stream, a);
             HIPCHK(hipGetLastError());
-            prim_scan_to_i64(ix->st, ix->tmp, d_tile_cnt.p, (size_t)ntiles, d_tile_off.p);
-            HIPCHK(hipMemcpyAsync(&nrows, d_tile_off.p + ntiles, sizeof nrows, hipMemcpyDeviceToHost, ix->st));
-            HIPCHK(hipStreamSynchronize(ix->st));
+            prim_scan_to_i64(stream, ix->lane[0].main.tmp, d_tile_cnt.p, (size_t)ntiles, d_tile_off.p);
+            HIPCHK(hipMemcpyAsync(&nrows, d_tile_off.p + ntiles, sizeof nrows, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
         }
-        hipLaunchKernelGGL(k_sd_records, dim3(sp_grid(nsel)), dim3(256), 0, ix->st, d_keys.p, L.off.p, d_coff.p, d_max.p, d_seeded.p, nsel, d_recs.p);
+        hipLaunchKernelGGL(k_sd_records, dim3(sp_grid(nsel)), dim3(256), 0, stream, d_keys.p, L.off.p, d_coff.p, d_max.p, d_seeded.p, nsel, d_recs.p);
         HIPCHK(hipGetLastError());
         if (nrows > 0) {
             try {
@@ -1116,16 +1121,16 @@ extern "C" lm_status lm_index_seed_distances(lm_index *ix, const uint64_t *keys,
                                 "index and the sorted positions (a larger min_dist reports fewer): " + e.what());
             }
             a.rows = d_rows.p;
-            hipLaunchKernelGGL(k_sd_pass<true>, dim3(grid), dim3(256), 0, ix->st, a);
+            hipLaunchKernelGGL(k_sd_pass<true>, dim3(grid), dim3(256), 0, stream, a);
             HIPCHK(hipGetLastError());
         }
         res->recs.resize((size_t)nsel);
         res->hist.resize(opt.hist_bins);
         res->rows.resize((size_t)nrows);
-        if (nsel > 0) HIPCHK(hipMemcpyAsync(res->recs.data(), d_recs.p, (size_t)nsel * sizeof(lm_seed_dist_rec), hipMemcpyDeviceToHost, ix->st));
-        if (opt.hist_bins > 0) HIPCHK(hipMemcpyAsync(res->hist.data(), d_hist.p, (size_t)opt.hist_bins * 8, hipMemcpyDeviceToHost, ix->st));
-        if (nrows > 0) HIPCHK(hipMemcpyAsync(res->rows.data(), d_rows.p, (size_t)nrows * sizeof(lm_seed_dist_row), hipMemcpyDeviceToHost, ix->st));
-        HIPCHK(hipStreamSynchronize(ix->st));
+        if (nsel > 0) HIPCHK(hipMemcpyAsync(res->recs.data(), d_recs.p, (size_t)nsel * sizeof(lm_seed_dist_rec), hipMemcpyDeviceToHost, stream));
+        if (opt.hist_bins > 0) HIPCHK(hipMemcpyAsync(res->hist.data(), d_hist.p, (size_t)opt.hist_bins * 8, hipMemcpyDeviceToHost, stream));
+        if (nrows > 0) HIPCHK(hipMemcpyAsync(res->rows.data(), d_rows.p, (size_t)nrows * sizeof(lm_seed_dist_row), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
     });
     if (st == LM_OK) *out = res.release();
     return st;
@@ -1372,12 +1377,12 @@ extern "C" lm_status lm_index_save(lm_index *ix, const char *dir_c, int chunks) 
                 for (int md = 2 * m0; md < 2 * m1; md++) {
                     const int64_t nm = md_off[(size_t)md + 1] - md_off[(size_t)md];
                     if (nm > 0)
-                        hipLaunchKernelGGL(lm::k_sp_dump_list, dim3(lm::sp_grid(nm)), dim3(256), 0, ix->st, ix->view, (uint32_t)md, nm,
+                        hipLaunchKernelGGL(lm::k_sp_dump_list, dim3(lm::sp_grid(nm)), dim3(256), 0, ix->lane[0].main.st, ix->view, (uint32_t)md, nm,
                                            dk.p + (md_off[(size_t)md] - s0), dv.p + (md_off[(size_t)md] - s0));
                 }
-                HIPCHK(hipMemcpyAsync(hk.data(), dk.p, (size_t)ns * 8, hipMemcpyDeviceToHost, ix->st));
-                HIPCHK(hipMemcpyAsync(hv.data(), dv.p, (size_t)ns * 8, hipMemcpyDeviceToHost, ix->st));
-                HIPCHK(hipStreamSynchronize(ix->st));
+                HIPCHK(hipMemcpyAsync(hk.data(), dk.p, (size_t)ns * 8, hipMemcpyDeviceToHost, ix->lane[0].main.st));
+                HIPCHK(hipMemcpyAsync(hv.data(), dv.p, (size_t)ns * 8, hipMemcpyDeviceToHost, ix->lane[0].main.st));
+                HIPCHK(hipStreamSynchronize(ix->lane[0].main.st));
             }
             const int64_t o0 = out_off[(size_t)2 * m0], o1 = out_off[(size_t)2 * m1], no = o1 - o0;
             std::vector<uint64_t> ok((size_t)no), ov((size_t)no);

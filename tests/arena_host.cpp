@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <thread>
 
 namespace fake {
 static size_t used = 0, limit = 0;
@@ -52,6 +53,7 @@ static const char *ErrStr(hipError_t e) { return e == hipSuccess ? "ok" : "fake 
 #define hipGetLastError() fake::Ok()
 #define hipDeviceSynchronize() fake::Ok()
 #define hipStreamSynchronize(s) fake::Ok()
+#define hipStreamDestroy(s) fake::Ok()
 #define hipMemsetAsync(p, v, n, s) fake::MemsetAsync((p), (v), (n), (s))
 #define hipGetErrorString(e) fake::ErrStr(e)
 #define hipHostMalloc(p, n, f) fake::Malloc((void **)(p), (n))
@@ -108,21 +110,58 @@ void *ah_dbuf_new(int phase) {
     return b;
 }
 void ah_dbuf_delete(void *b) { delete (lm::DBuf<uint8_t> *)b; }
-// 0 ok, 1 DeviceOOM
-int ah_dbuf_ensure(void *b, size_t n, void *arena) {
-    lm::tls_arena = (lm::ScratchArena *)arena;
-    int rc = 0;
+// a handle for its two lanes (arena, streams that stay null over the fake device, rocPRIM storage)
+void *ah_index_new() { return new lm_index(); }
+void ah_index_delete(void *ix) { delete (lm_index *)ix; }
+void *ah_index_arena(void *ix, int lane) { return &((lm_index *)ix)->lane[lane].arena; }
+// the calling thread's binding, installed and taken back through the guard only (scopes nest: pop in reverse order)
+void *ah_bind_push(void *ix, int lane, int producer) {
+    lm::Lane &ln = ((lm_index *)ix)->lane[lane];
+    return new lm::BindScope((lm_index *)ix, lane, producer ? ln.producer : ln.main);
+}
+void ah_bind_pop(void *scope) { delete (lm::BindScope *)scope; }
+int ah_bound_lane() { return lm::tls_bind.lane; }
+void *ah_bound_arena() { return lm::tls_bind.arena; }
+// is the thread bound to (lane, main / producer) of ix, field for field?  ix null: is it unbound?
+int ah_bound_is(void *ix, int lane, int producer) {
+    const lm::ThreadBind &t = lm::tls_bind;
+    if (!ix) return t.lane == 0 && !t.stream && !t.tmp && !t.arena;
+    lm::Lane &ln = ((lm_index *)ix)->lane[lane];
+    lm::StreamCtx &sc = producer ? ln.producer : ln.main;
+    return t.lane == lane && t.stream == sc.st && t.tmp == &sc.tmp && t.arena == &ln.arena;
+}
+// what a thread started now finds as its binding: 1 unbound
+int ah_fresh_thread_is_unbound() {
+    int r = 0;
+    std::thread t([&] { r = ah_bound_is(nullptr, 0, 0); });
+    t.join();
+    return r;
+}
+// 0 ok, 1 DeviceOOM; allocates under the calling thread's binding
+int ah_dbuf_ensure_bound(void *b, size_t n) {
     try {
         ((lm::DBuf<uint8_t> *)b)->ensure(n);
     } catch (const lm::DeviceOOM &) {
-        rc = 1;
+        return 1;
     }
-    lm::tls_arena = nullptr;
-    return rc;
+    return 0;
 }
+// the same inside a scope bound to (lane, main) of ix, which a DeviceOOM leaves by unwinding
+int ah_dbuf_ensure_in_scope(void *b, size_t n, void *ix, int lane) {
+    try {
+        lm::BindScope bind((lm_index *)ix, lane, ((lm_index *)ix)->lane[lane].main);
+        ((lm::DBuf<uint8_t> *)b)->ensure(n);
+    } catch (const lm::DeviceOOM &) {
+        return 1;
+    }
+    return 0;
+}
+// ... bound to lane 0 of ix (null: unbound)
+int ah_dbuf_ensure(void *b, size_t n, void *ix) { return ix ? ah_dbuf_ensure_in_scope(b, n, ix, 0) : ah_dbuf_ensure_bound(b, n); }
 void ah_dbuf_release(void *b) { ((lm::DBuf<uint8_t> *)b)->release(); }
 void *ah_dbuf_ptr(void *b) { return ((lm::DBuf<uint8_t> *)b)->p; }
 size_t ah_dbuf_cap(void *b) { return ((lm::DBuf<uint8_t> *)b)->cap; }
 int ah_dbuf_in_arena(void *b) { return ((lm::DBuf<uint8_t> *)b)->arena != nullptr; }
+void *ah_dbuf_arena(void *b) { return ((lm::DBuf<uint8_t> *)b)->arena; }
 long long ah_dbuf_bytes_total() { return lm::g_dbuf_bytes.load(); }
 }

@@ -34,8 +34,16 @@ def L():
         subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__",
                                "-I/opt/rocm/include", "-o", LIB, SRC])
     lib = C.CDLL(LIB)
-    for f in ("ah_arena_new", "ah_arena_alloc", "ah_dbuf_new", "ah_dbuf_ptr"):
+    for f in ("ah_arena_new", "ah_arena_alloc", "ah_dbuf_new", "ah_dbuf_ptr", "ah_index_new", "ah_index_arena", "ah_bind_push", "ah_bound_arena",
+              "ah_dbuf_arena"):
         getattr(lib, f).restype = C.c_void_p
+    for f in ("ah_index_delete", "ah_bind_pop", "ah_dbuf_arena"):
+        getattr(lib, f).argtypes = [C.c_void_p]
+    lib.ah_index_arena.argtypes = [C.c_void_p, C.c_int]
+    lib.ah_bind_push.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    lib.ah_bound_is.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    lib.ah_dbuf_ensure_bound.argtypes = [C.c_void_p, C.c_size_t]
+    lib.ah_dbuf_ensure_in_scope.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]
     lib.ah_arena_alloc.argtypes = [C.c_void_p, C.c_size_t]
     lib.ah_arena_release.argtypes = [C.c_void_p, C.c_void_p]
     for f in ("ah_arena_delete", "ah_arena_trim", "ah_dbuf_delete", "ah_dbuf_release"):
@@ -155,25 +163,60 @@ def test_empty_slabs_are_handed_back_before_giving_up_and_oom_is_reported(L):
 
 def test_dbuf_phase_buffers_use_the_arena_and_small_or_plain_ones_do_not(L):
     L.ah_reset(2048 * MB)
-    a = L.ah_arena_new()
+    ix = L.ah_index_new()              # (a thread is bound to a lane of a handle: the arena is lane 0's)
+    a = L.ah_index_arena(ix, 0)
     base = L.ah_dbuf_bytes_total()
     big, small, plain = L.ah_dbuf_new(1), L.ah_dbuf_new(1), L.ah_dbuf_new(0)
-    assert L.ah_dbuf_ensure(big, 100 * MB, a) == 0 and L.ah_dbuf_in_arena(big) == 1
+    assert L.ah_dbuf_ensure(big, 100 * MB, ix) == 0 and L.ah_dbuf_in_arena(big) == 1
     assert L.ah_dbuf_cap(big) >= 100 * MB                         # 1/8 head room
-    assert L.ah_dbuf_ensure(small, 1 * MB, a) == 0 and L.ah_dbuf_in_arena(small) == 0   # below 32 MB: plain
-    assert L.ah_dbuf_ensure(plain, 100 * MB, a) == 0 and L.ah_dbuf_in_arena(plain) == 0  # not a phase buffer
-    assert L.ah_dbuf_ensure(big, 10 * MB, a) == 0                 # grow-only: no change
+    assert L.ah_dbuf_ensure(small, 1 * MB, ix) == 0 and L.ah_dbuf_in_arena(small) == 0   # below 32 MB: plain
+    assert L.ah_dbuf_ensure(plain, 100 * MB, ix) == 0 and L.ah_dbuf_in_arena(plain) == 0  # not a phase buffer
+    assert L.ah_dbuf_ensure(big, 10 * MB, ix) == 0                 # grow-only: no change
     p0 = L.ah_dbuf_ptr(big)
-    assert L.ah_dbuf_ensure(big, 300 * MB, a) == 0 and L.ah_dbuf_in_arena(big) == 1
+    assert L.ah_dbuf_ensure(big, 300 * MB, ix) == 0 and L.ah_dbuf_in_arena(big) == 1
     L.ah_dbuf_release(big)
     assert L.ah_arena_live_bytes(a) == 0
     again = L.ah_dbuf_new(1)
-    assert L.ah_dbuf_ensure(again, 300 * MB, a) == 0              # carved from the slab the released buffer left
+    assert L.ah_dbuf_ensure(again, 300 * MB, ix) == 0              # carved from the slab the released buffer left
     assert L.ah_arena_slab_allocs(a) == 2 and p0 is not None
-    assert L.ah_dbuf_ensure(again, 4000 * MB, a) == 1             # beyond the fake device: DeviceOOM, buffer empty
+    assert L.ah_dbuf_ensure(again, 4000 * MB, ix) == 1             # beyond the fake device: DeviceOOM, buffer empty
     assert L.ah_dbuf_ptr(again) is None and L.ah_dbuf_cap(again) == 0
     for b in (big, small, plain, again):
         L.ah_dbuf_delete(b)
     assert L.ah_dbuf_bytes_total() == base
-    L.ah_arena_delete(a)
+    L.ah_index_delete(ix)
+    assert L.ah_device_used() == 0
+
+
+def test_a_thread_binding_nests_and_comes_back_when_a_scope_is_left(L):
+    """lm::BindScope is the only writer of the thread's binding (lane, stream, rocPRIM storage, arena): phase buffers follow
+    it, a nested scope gives the outer binding back - also when DeviceOOM unwinds through it - and another thread starts unbound."""
+    L.ah_reset(4096 * MB)
+    ix = L.ah_index_new()
+    A, B = L.ah_index_arena(ix, 0), L.ah_index_arena(ix, 1)
+    assert A is not None and B is not None and A != B
+    bufs = [L.ah_dbuf_new(1) for _ in range(5)]
+    n = 64 * MB
+    assert L.ah_bound_is(None, 0, 0) == 1
+    assert L.ah_dbuf_ensure_bound(bufs[0], n) == 0 and L.ah_dbuf_in_arena(bufs[0]) == 0     # unbound: a plain device allocation
+    outer = L.ah_bind_push(ix, 0, 0)
+    assert L.ah_bound_is(ix, 0, 0) == 1
+    assert L.ah_dbuf_ensure_bound(bufs[1], n) == 0 and L.ah_dbuf_arena(bufs[1]) == A
+    inner = L.ah_bind_push(ix, 1, 1)
+    assert L.ah_bound_is(ix, 1, 1) == 1 and L.ah_bound_lane() == 1
+    assert L.ah_dbuf_ensure_bound(bufs[2], n) == 0 and L.ah_dbuf_arena(bufs[2]) == B
+    L.ah_bind_pop(inner)
+    assert L.ah_bound_is(ix, 0, 0) == 1
+    assert L.ah_dbuf_ensure_bound(bufs[3], n) == 0 and L.ah_dbuf_arena(bufs[3]) == A
+    assert L.ah_fresh_thread_is_unbound() == 1                                              # started while this thread is bound
+    L.ah_reset(L.ah_device_used() + n // 2)                                                 # the device cannot serve the next request
+    assert L.ah_dbuf_ensure_in_scope(bufs[4], n, ix, 1) == 1                                # DeviceOOM inside a nested scope
+    assert L.ah_dbuf_ptr(bufs[4]) is None
+    assert L.ah_bound_is(ix, 0, 0) == 1 and L.ah_bound_arena() == A                         # ... and the outer binding is back
+    L.ah_reset(4096 * MB)
+    L.ah_bind_pop(outer)
+    assert L.ah_bound_is(None, 0, 0) == 1
+    for b in bufs:
+        L.ah_dbuf_delete(b)
+    L.ah_index_delete(ix)
     assert L.ah_device_used() == 0
