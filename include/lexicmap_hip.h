@@ -146,12 +146,17 @@ lm_status lm_index_get_residency(const lm_index *idx, lm_residency_info *info);
  *     finish succeeds or not; after a failure lm_last_error(NULL) has the text.  LM_ERR_ARG when nothing was added.
  * Not done here (nor by the reference at this point): reading FASTA / gz files, soft-masking, --max-kmer-freq (genomes are
  * ADDED to a resident index by lm_index_builder_extend, resident indexes are joined and subset by
- * lm_index_builder_add_index; joining SHARDS is not done); k must be 31 and the mask set may have at most two masks per p-base prefix (masks <= 2 * 4^p). */
+ * lm_index_builder_add_index; joining SHARDS is not done).
+ * Only the GENERATED masks are limited: lm_index_builder_new makes its own mask set, and that generator takes k = 31 and puts
+ * at most two masks on a p-base prefix (masks <= 2 * 4^p).  lm_index_builder_new_masks builds with the caller's masks - any
+ * k in [10, 32], up to 32 masks on a prefix - and _extend, _like and _add_index take whatever set their index carries under
+ * the same rule. */
 typedef struct lm_build_opt {      /* lm_build_opt_default(): the defaults of `lexicmap index` (index.go:538-619) */
-    int32_t k;                     /* 31 (only 31 is accepted, as in lm_index_build_synthetic) */
-    int32_t masks;                 /* 20000; [4, 65535] with at most two masks per p-base prefix, p = max(1, floor(log4 masks)):
-                                    * 4..8, 16..32, 64..128, 256..512, 1024..2048, 4096..8192, 16384..32768; others: LM_ERR_ARG */
-    int64_t mask_seed;             /* 1 */
+    int32_t k;                     /* 31.  _new (generated masks) and lm_index_build_synthetic: only 31; _new_masks: [10, 32] */
+    int32_t masks;                 /* 20000.  _new: [4, 65535] with at most two masks per p-base prefix, p = max(1, floor(log4 masks)):
+                                    * 4..8, 16..32, 64..128, 256..512, 1024..2048, 4096..8192, 16384..32768; others: LM_ERR_ARG.
+                                    * _new_masks: ignored (its nmasks rules) */
+    int64_t mask_seed;             /* 1.  _new_masks: not used to build, written to info.toml as rand-seed */
     int32_t max_desert, seed_dist; /* 100, 50 */
     int32_t contig_interval;       /* 1000 */
     int32_t genome_batch_size;     /* 5000; [1, 2^17] */
@@ -164,7 +169,21 @@ typedef struct lm_contig {
 } lm_contig;
 typedef struct lm_index_builder lm_index_builder;
 void lm_build_opt_default(lm_build_opt *o);
+/* A builder with a mask set generated here from bo->mask_seed (not lexichash's generator).  Only these generated masks are
+ * limited: k == 31 and bo->masks <= 2 * 4^p, else LM_ERR_ARG. */
 lm_status lm_index_builder_new(const lm_build_opt *bo, const lm_options *opt, const lm_residency *res, int device, lm_index_builder **out);
+/* As lm_index_builder_new, with the caller's mask set (`lexicmap index -M/--mask-file`: the masks `lexicmap utils masks`
+ * printed for an existing index, so that the new index can be joined with it).  bo->k is the k of the masks, bo->masks is
+ * ignored (nmasks rules), bo->mask_seed is not used to build and is what lm_index_save writes as rand-seed.  The masks are
+ * copied before the call returns.  Accepted: k in [10, 32]; nmasks in [4, 65535]; masks strictly ascending and below 4^k;
+ * with p = max(floor(log4 nmasks), 1) every p-base prefix has at least one mask and none more than 32.  Anything else is
+ * LM_ERR_ARG and lm_last_error(NULL) names the first offending mask (0-based), the first prefix without a mask, or the prefix
+ * with too many and its count.  The option checks of _new apply unchanged (min_prefix against k and p + anchor_prefix, ...).
+ * A set in which every prefix has one mask or two gives the very index _new gives for the same masks.  add, add_index,
+ * finish, free, last_error, sharding by opt->shard_count, residency, save, mask_seeds, seed_positions and seed_distances
+ * work as with _new. */
+lm_status lm_index_builder_new_masks(const lm_build_opt *bo, const uint64_t *masks, size_t nmasks, const lm_options *opt,
+                                     const lm_residency *res, int device, lm_index_builder **out);
 lm_status lm_index_builder_add(lm_index_builder *b, const char *genome_id, const lm_contig *contigs, size_t ncontigs);
 lm_status lm_index_builder_finish(lm_index_builder *b, lm_index **out); /* consumes b on success and on failure */
 void lm_index_builder_free(lm_index_builder *b);                        /* abandon */

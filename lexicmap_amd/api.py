@@ -171,6 +171,8 @@ def lib():
     L.lm_build_opt_default.argtypes = [C.POINTER(BuildOpt)]
     L.lm_build_opt_default.restype = None
     L.lm_index_builder_new.argtypes = [C.POINTER(BuildOpt), C.POINTER(Options), C.POINTER(Residency), C.c_int, C.POINTER(vp)]
+    L.lm_index_builder_new_masks.argtypes = [C.POINTER(BuildOpt), C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(Options),
+                                             C.POINTER(Residency), C.c_int, C.POINTER(vp)]
     L.lm_index_builder_extend.argtypes = [vp, C.POINTER(BuildOpt), C.POINTER(Residency), C.POINTER(vp)]
     L.lm_index_builder_like.argtypes = [vp, C.POINTER(BuildOpt), C.POINTER(Residency), C.POINTER(vp)]
     L.lm_index_builder_add_index.argtypes = [vp, vp, C.POINTER(C.c_uint64), C.c_size_t]
@@ -328,12 +330,13 @@ class Index:
         return cls(None, opt, device, _handle=h)
 
     @classmethod
-    def from_genomes(cls, genomes, build_opt=None, options=None, device=0, residency=None):
+    def from_genomes(cls, genomes, build_opt=None, options=None, device=0, residency=None, masks=None):
         """index built on the GPU from caller-supplied genomes (lm_index_builder_*): genomes is a list of
         (genome_id, [(contig_id, seq bytes), ...]); build_opt a BuildOpt (None: the defaults of `lexicmap index`); residency as
         in __init__.  A genome the builder refuses (LM_ERR_ARG: a contig longer than max_genome, a record shorter than k)
-        raises ValueError with the builder's text; nothing of it is added."""
-        b = IndexBuilder(build_opt, options, device, residency)
+        raises ValueError with the builder's text; nothing of it is added.  masks: the mask set to build with, as in
+        IndexBuilder (None: the set generated from build_opt.mask_seed)."""
+        b = IndexBuilder(build_opt, options, device, residency, masks)
         try:
             for gid, contigs in genomes:
                 b.add(gid, contigs)
@@ -410,6 +413,13 @@ class Index:
         i = IndexInfo()
         lib().lm_index_get_info(self.h, C.byref(i))
         return {f[0]: getattr(i, f[0]) for f in IndexInfo._fields_}
+
+    def masks(self):
+        """the masks of the handle (lm_index_masks) as a numpy uint64 copy: what IndexBuilder(masks=...) and write_mask_file take"""
+        import numpy as np
+        M = self.info()["masks"]
+        p = lib().lm_index_masks(self.h)
+        return np.ctypeslib.as_array(p, shape=(M,)).astype(np.uint64, copy=True)
 
     def mask_seeds(self, mask):
         """(k-mers, values) stored under one mask as numpy uint64 arrays (reference value layout)"""
@@ -738,18 +748,33 @@ class Index:
 class IndexBuilder:
     """lm_index_builder: genomes are added one at a time (the host may stream them), finish() returns the Index"""
 
-    def __init__(self, build_opt=None, options=None, device=0, residency=None):
+    def __init__(self, build_opt=None, options=None, device=0, residency=None, masks=None):
+        """masks: None makes the plain lm_index_builder_new call (a mask set generated from build_opt.mask_seed; k = 31 only).
+        A sequence or numpy array of uint64 builds with exactly those masks (lm_index_builder_new_masks: build_opt.k is their
+        k, build_opt.masks is ignored) - e.g. Index.masks() of another index or read_mask_file(); a set the library refuses
+        (LM_ERR_ARG) raises ValueError with its text."""
         L = lib()
         self.opt = options or default_options()
         self.bo = build_opt or BuildOpt.default()
         self.device = device
         h = C.c_void_p()
-        st = L.lm_index_builder_new(C.byref(self.bo), C.byref(self.opt), C.byref(residency) if residency is not None else None,
-                                    device, C.byref(h))
-        if st != 0:
-            e = RuntimeError("lm_index_builder_new failed (%d): %s" % (st, L.lm_last_error(None).decode()))
-            e.status = st
-            raise e
+        res = C.byref(residency) if residency is not None else None
+        if masks is None:
+            st = L.lm_index_builder_new(C.byref(self.bo), C.byref(self.opt), res, device, C.byref(h))
+            if st != 0:
+                e = RuntimeError("lm_index_builder_new failed (%d): %s" % (st, L.lm_last_error(None).decode()))
+                e.status = st
+                raise e
+        else:
+            import numpy as np
+            ms = np.ascontiguousarray(masks, dtype=np.uint64).reshape(-1)  # (the library copies them before it returns)
+            st = L.lm_index_builder_new_masks(C.byref(self.bo), ms.ctypes.data_as(C.POINTER(C.c_uint64)), ms.size, C.byref(self.opt),
+                                              res, device, C.byref(h))
+            if st != 0:
+                text = L.lm_last_error(None).decode()
+                e = ValueError(text) if st == 7 else RuntimeError("lm_index_builder_new_masks failed (%d): %s" % (st, text))
+                e.status = st
+                raise e
         self.h = h
 
     @classmethod
@@ -853,6 +878,59 @@ class IndexBuilder:
         if self.h:
             lib().lm_index_builder_free(self.h)
             self.h = None
+
+
+def write_mask_file(path, k, masks):
+    """a mask set in the text form `lexicmap utils masks` prints and `lexicmap index -M/--mask-file` reads: one mask per
+    line, `<1-based number>\\t<k-mer>`, A = 0, C = 1, G = 2, T = 3 with the first base in the highest bits; gzip-compressed
+    when path ends in .gz.  Host-side file work, like FASTA reading."""
+    import gzip
+    k = int(k)
+    if not 1 <= k <= 32:
+        raise ValueError("write_mask_file: k = %d is outside [1, 32]" % k)
+    lines = []
+    for i, m in enumerate(masks):
+        m = int(m)
+        if m < 0 or m >> (2 * k):
+            raise ValueError("write_mask_file: mask %d is not below 4^k (k = %d)" % (i, k))
+        lines.append("%d\t%s\n" % (i + 1, "".join("ACGT"[(m >> (2 * (k - 1 - j))) & 3] for j in range(k))))
+    op = gzip.open if str(path).endswith(".gz") else open
+    with op(path, "wb") as f:
+        f.write("".join(lines).encode())
+
+
+def read_mask_file(path):
+    """-> (k, numpy uint64 array): the masks of a file in the form of write_mask_file, in file order.  ValueError for lines of
+    different k-mer lengths, a letter outside ACGT (either case), numbers that are not 1..n in order, or no mask at all."""
+    import gzip
+    import numpy as np
+    op = gzip.open if str(path).endswith(".gz") else open
+    with op(path, "rb") as f:
+        text = f.read().decode("ascii", "replace")
+    code = {"A": 0, "C": 1, "G": 2, "T": 3}
+    k, out = None, []
+    for ln, line in enumerate(text.splitlines(), 1):
+        if not line.strip():
+            continue
+        cols = line.rstrip("\r").split("\t")
+        if len(cols) < 2 or not cols[0].strip().isdigit() or int(cols[0]) != len(out) + 1:
+            raise ValueError("%s line %d: expected mask number %d and a k-mer separated by a tab" % (path, ln, len(out) + 1))
+        kmer = cols[1].strip().upper()
+        if k is None:
+            k = len(kmer)
+            if not 1 <= k <= 32:
+                raise ValueError("%s line %d: a k-mer of %d bases (1..32 fit a mask)" % (path, ln, k))
+        elif len(kmer) != k:
+            raise ValueError("%s line %d: a k-mer of %d bases after k-mers of %d" % (path, ln, len(kmer), k))
+        v = 0
+        for c in kmer:
+            if c not in code:
+                raise ValueError("%s line %d: letter %r is not one of ACGT" % (path, ln, c))
+            v = (v << 2) | code[c]
+        out.append(v)
+    if not out:
+        raise ValueError("%s holds no mask" % path)
+    return k, np.array(out, dtype=np.uint64)
 
 
 def format_rows(rows, ids, lens, flags=0, want_text=True):

@@ -28,6 +28,7 @@
 #include "lm_internal.h"
 #include "lm_prims.h"
 #include "lm_build_plan.h"
+#include "lm_mask_plan.h"
 #include "lm_join_plan.h"
 
 namespace lm {
@@ -171,7 +172,8 @@ __device__ __forceinline__ int desert_capturing_mask(const MaskTab &mt, const ui
     const uint32_t pf = (uint32_t)(x >> shift);
     const int j0 = mt.pfx_first[pf], j1 = mt.pfx_first[pf + 1];
     if (j0 >= j1) return -1;
-    // one sweep of the window for all (one or two) masks of the prefix: bit j - j0 = x is beaten for mask j
+    // one sweep of the window for all masks of the prefix (1 .. 32: lm_mask_plan.h refuses a set with more): bit j - j0 = x is
+    // beaten for mask j
     uint32_t beaten = 0;
     for (int w = lane; w < nk; w += 64) {
         uint32_t pfw, prc;
@@ -314,9 +316,11 @@ __global__ void k_pack_record(const uint8_t *__restrict__ ascii, const int64_t *
 
 // LexicHash capture of one record by one workgroup, all phases in one launch.  LDS = true: the per-mask minima live in LDS
 // (M x 8 B = 160 KB for the default 20000 masks: the whole LDS of a CU) instead of a global table hammered with atomics;
-// false (more masks than a CU's LDS holds): in ghash[block][M].  Masks of a p-base prefix are found without a table in
-// memory: in a lexicmap mask set every prefix has one mask and some have two (docs/content/usage/utils/masks.md:69-110),
-// so first(pf) = pf + #doubled prefixes below pf: a 4^p-bit map + per-word counts (2.5 KB).
+// false (more masks than a CU's LDS holds): in ghash[block][M].  CSR = false: the masks of a p-base prefix are found without
+// a table in memory: in a lexicmap mask set every prefix has one mask and some have two
+// (docs/content/usage/utils/masks.md:69-110), so first(pf) = pf + #doubled prefixes below pf: a 4^p-bit map + per-word counts
+// (2.5 KB).  CSR = true (a caller's or an opened index's set with three or more masks on some prefix): from the prefix table
+// mt.pfx_first, copied to LDS where the host found room for it (TLDS).  Only phase 1 and the prefix part of phase 2 differ.
 // Phase 1: ds_min_u64 of mask^kmer over the k-mers sharing a mask's prefix, k-mers that overlap a skip region left out.
 // Phase 1b, the missing-prefix rule: a mask whose minimum is still untouched takes the argmin over ALL
 // k-mers of both strands - one lane per such mask, the k-mers cut 64 at a time and passed round the wavefront; the lane also
@@ -332,7 +336,16 @@ template <bool LDS> __device__ __forceinline__ unsigned long long cap_min_load(c
     if (LDS) return *p;
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-template <bool LDS>
+// The masks [j0, j0 + nj) of the p-base prefix pf (a macro: the CSR = false instantiations keep the statements, and so the code,
+// they had before there was a second way).  CSR = false: from the doubled-prefix map, which needs every prefix once or
+// twice (every generated set).  CSR = true: from the prefix table pt, 4^p + 1 entries (any set lm_mask_plan.h accepts: up to
+// 32 masks on a prefix), which is mt.pfx_first in global memory or the workgroup's copy of it in LDS (TLDS).
+#define LM_PREFIX_MASKS(pf)                                                                                                \
+    const unsigned long long w = CSR ? 0ull : bm[(pf) >> 6];                                                               \
+    const int j0 = CSR ? pt[(pf)] : (int)((pf) + bc[(pf) >> 6] + (uint32_t)__popcll(w & ((1ull << ((pf) & 63)) - 1)));      \
+    const int nj = CSR ? pt[(pf) + 1] - j0 : 1 + (int)((w >> ((pf) & 63)) & 1ull);
+// LDS of the CSR instantiations: the minima [M] (LDS), the wave totals of phase 2 [16], the prefix table [4^p + 1] (TLDS)
+template <bool LDS, bool CSR, bool TLDS>
 __global__ __launch_bounds__(1024) void k_capture_g(GenomeTab gt, MaskTab mt, const uint8_t *__restrict__ gbits, int64_t l0,
                                                     const uint64_t *__restrict__ dbl_map, const uint32_t *__restrict__ dbl_cnt,
                                                     unsigned long long *__restrict__ ghash, uint32_t *__restrict__ miss_pos,
@@ -347,8 +360,10 @@ __global__ __launch_bounds__(1024) void k_capture_g(GenomeTab gt, MaskTab mt, co
     const bool stamp = clk && blockIdx.x == 0 && threadIdx.x == 0; // LM_DEBUG: the phases of the chunk's first record (100-MHz clock)
     if (stamp) clk[0] = wall_clock64();
     unsigned long long *hs = LDS ? lds_dyn : ghash + (int64_t)c * mt.M;  // [M]
-    unsigned long long *bm = LDS ? lds_dyn + mt.M : lds_dyn;             // [nw]
+    unsigned long long *bm = LDS ? lds_dyn + mt.M : lds_dyn;             // [nw]  (CSR: the wave totals and the table start here)
     uint32_t *bc = (uint32_t *)(bm + nw);                                // [nw]
+    int32_t *pl = (int32_t *)bm + 16;                                    // [4^p + 1]  (TLDS)
+    const int32_t *pt = TLDS ? pl : mt.pfx_first;
     uint32_t *mp = miss_pos + (int64_t)c * mt.M, *mc = miss_cnt + (int64_t)c * mt.M;
     const int64_t l = l0 + c;
     const uint8_t *gb = gbits + gt.g_off[l];
@@ -358,10 +373,13 @@ __global__ __launch_bounds__(1024) void k_capture_g(GenomeTab gt, MaskTab mt, co
     const int shift = (mt.K - mt.p) << 1;
     const int lane = threadIdx.x & 63;
     for (int i = threadIdx.x; i < mt.M; i += blockDim.x) hs[i] = ~0ull;
-    for (int i = threadIdx.x; i < nw; i += blockDim.x) {
-        bm[i] = dbl_map[i];
-        bc[i] = dbl_cnt[i];
-    }
+    if (!CSR)
+        for (int i = threadIdx.x; i < nw; i += blockDim.x) {
+            bm[i] = dbl_map[i];
+            bc[i] = dbl_cnt[i];
+        }
+    if (TLDS)
+        for (int i = threadIdx.x; i <= (1 << (2 * mt.p)); i += blockDim.x) pl[i] = mt.pfx_first[i];
     __syncthreads();
     for (int pos = threadIdx.x; pos < npos; pos += blockDim.x) {
         if (kmer_skipped(rs, re, nreg, pos, mt.K)) continue;
@@ -371,9 +389,7 @@ __global__ __launch_bounds__(1024) void k_capture_g(GenomeTab gt, MaskTab mt, co
         for (int s = 0; s < 2; s++) {
             const uint64_t x = s ? rc : fwd;
             const uint32_t pf = (uint32_t)(x >> shift);
-            const unsigned long long w = bm[pf >> 6];
-            const int j0 = (int)(pf + bc[pf >> 6] + (uint32_t)__popcll(w & ((1ull << (pf & 63)) - 1)));
-            const int nj = 1 + (int)((w >> (pf & 63)) & 1ull);
+            LM_PREFIX_MASKS(pf)
             for (int j = j0; j < j0 + nj; j++) {
                 const unsigned long long h = mt.masks[j] ^ x;
                 if (h < hs[j]) atomicMin(&hs[j], h);
@@ -436,7 +452,7 @@ __global__ __launch_bounds__(1024) void k_capture_g(GenomeTab gt, MaskTab mt, co
     const uint64_t bg = gt.g_bg[l];
     // ---- phase 2: count, reserve ONE contiguous range of the staging arrays for the record (a per-capture atomic on the
     // shared counter costs more than the whole sweep), write
-    uint32_t *wsum = bc + nw; // [16] wave totals
+    uint32_t *wsum = CSR ? (uint32_t *)bm : bc + nw; // [16] wave totals
     __shared__ unsigned long long base_seed, base_pos;
     uint32_t mine = 0;
     for (int sweep = 0; sweep < 2; sweep++) {
@@ -482,9 +498,7 @@ __global__ __launch_bounds__(1024) void k_capture_g(GenomeTab gt, MaskTab mt, co
             for (int s = 0; s < 2; s++) {
                 const uint64_t x = s ? rc : fwd;
                 const uint32_t pf = (uint32_t)(x >> shift);
-                const unsigned long long w = bm[pf >> 6];
-                const int j0 = (int)(pf + bc[pf >> 6] + (uint32_t)__popcll(w & ((1ull << (pf & 63)) - 1)));
-                const int nj = 1 + (int)((w >> (pf & 63)) & 1ull);
+                LM_PREFIX_MASKS(pf)
                 for (int j = j0; j < j0 + nj; j++) {
                     if ((mt.masks[j] ^ x) != cap_min_load<LDS>(&hs[j])) continue;
                     if (x == 0 || lm_low_complexity(x, mt.K)) continue;
@@ -541,25 +555,25 @@ __global__ void k_pseudo_pos_g(GenomeTab gt, int64_t l0, int nchunk, int K, uint
 // max_desert apart, walk from pre + seed_dist in steps of seed_dist; at each step scan seed_pos_r positions upstream, then
 // downstream, for a non-low-complexity k-mer (+ strand before - strand) that IS THE CAPTURE OF SOME MASK WHEN THE WINDOW
 // [pre - 1000, pos + 1000 + k) ALONE IS MASKED (MaskKnownDistinctPrefixes(window, nil, false), :1191-1240), and store it
-// under that mask - the LAST (largest-index) mask that captures it.  A wavefront takes 64 seed pairs, finds the deserts
+// under that mask - the LAST (largest-index) mask that captures it.  A wavefront takes ppw (at most 64) seed pairs, finds the deserts
 // among them and walks them one after the other; the capture test of a candidate is a sweep of the window by the 64 lanes
 // (is any window k-mer of either strand with the same p-base prefix closer to the mask?).  The walk starts from pre = 0
 // and ends at the pseudo position len - K of THAT record, the window is clipped to that record, and a candidate whose
 // k-mer overlaps a skip region is passed over in the upstream and in the downstream scan (add_one's in_intervals) - the
 // window masking itself ignores skip regions (MaskKnownDistinctPrefixes(window, nil, false), lib-index-build.go:1198).
 __global__ __launch_bounds__(256) void k_desert_fill_g(GenomeTab gt, MaskTab mt, const uint8_t *__restrict__ gbits, int64_t l0,
-                                                        const uint64_t *__restrict__ pos_keys, int64_t npk, int max_desert,
+                                                        const uint64_t *__restrict__ pos_keys, int64_t npk, int ppw, int max_desert,
                                                         int seed_dist, uint16_t *__restrict__ s_mask,
                                                         uint64_t *__restrict__ s_kmer, uint64_t *__restrict__ s_val,
                                                         unsigned long long *__restrict__ counter, unsigned long long cap) {
     const int seed_pos_r = seed_dist / 2;
     const int lane = threadIdx.x & 63;
     const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
-    for (int64_t base = wave * 64; base < npk; base += nwaves * 64) {
+    for (int64_t base = wave * ppw; base < npk; base += nwaves * ppw) { // ppw (1 .. 64) seed pairs per wavefront
         const int64_t t = base + lane;
         int c = 0, pos = 0, pre = 0;
         bool isd = false;
-        if (t < npk) {
+        if (lane < ppw && t < npk) {
             const uint64_t key = pos_keys[t];
             c = (int)(key >> 32);
             pos = (int)((key & 0xffffffffu) >> 1);
@@ -747,23 +761,34 @@ struct PinnedOOM : DeviceOOM {
 };
 
 // The settings of the seed pipeline, checked once for all front ends; false: `err` says what is wrong (LM_ERR_ARG).
-// gen_masks puts every p-base prefix once and the rest on distinct prefixes, so it makes at most 2 * 4^p masks; a desert
-// walk advances by seed_dist.
-static bool seed_settings_ok(const char *who, int k, int masks, int max_desert, int seed_dist, std::string &err) {
+// Only the GENERATED masks are limited to k = 31 and 2 * 4^p masks: gen_masks puts every p-base prefix once and the rest on
+// distinct prefixes.  A set that is given - by the caller (lm_index_builder_new_masks) or by the resident index that is
+// continued - may have any k and shape lm_mask_plan.h accepts; builder_header checks it.  A desert walk advances by seed_dist.
+static bool seed_settings_ok(const char *who, int k, int masks, int max_desert, int seed_dist, bool generated, std::string &err) {
+    if (!generated) {
+        if (k < MASK_PLAN_MIN_K || k > MASK_PLAN_MAX_K || masks < MASK_PLAN_MIN_MASKS || masks > MASK_PLAN_MAX_MASKS || max_desert < 1 || seed_dist < 1) {
+            err = std::string(who) + ": unsupported settings (k = " + std::to_string(k) + " must be in [10, 32], the number of masks = " + std::to_string(masks) +
+                  " in [4, 65535], max_desert and seed_dist >= 1)";
+            return false;
+        }
+        return true;
+    }
     if (k != 31 || masks < 4 || masks > 65535 || max_desert < 1 || seed_dist < 1) {
-        err = std::string(who) + ": unsupported settings (k must be 31, masks in [4, 65535], max_desert and seed_dist >= 1)";
+        err = std::string(who) + ": unsupported settings (k must be 31, masks in [4, 65535], max_desert and seed_dist >= 1; only the generated masks "
+              "are limited to k = 31: lm_index_builder_new_masks takes the caller's masks with k in [10, 32])";
         return false;
     }
     const int p = mask_prefix_of(masks);
     if (masks > 2 * (1 << (2 * p))) {
         err = std::string(who) + ": " + std::to_string(masks) + " masks need more than two masks per " + std::to_string(p) +
-              "-base prefix, which the mask generator of this build does not make (at most " + std::to_string(2 * (1 << (2 * p))) + ")";
+              "-base prefix, which the mask generator of this build does not make (at most " + std::to_string(2 * (1 << (2 * p))) +
+              "; only the generated masks are limited: lm_index_builder_new_masks takes up to 32 masks on a prefix)";
         return false;
     }
     return true;
 }
-static bool build_opt_ok(const char *who, const lm_build_opt &bo, std::string &err) {
-    if (!seed_settings_ok(who, bo.k, bo.masks, bo.max_desert, bo.seed_dist, err)) return false;
+static bool build_opt_ok(const char *who, const lm_build_opt &bo, bool generated, std::string &err) {
+    if (!seed_settings_ok(who, bo.k, bo.masks, bo.max_desert, bo.seed_dist, generated, err)) return false;
     if (bo.genome_batch_size < 1 || bo.genome_batch_size > (1 << 17) || bo.contig_interval < 0 || bo.contig_interval >= (1 << 28) ||
         bo.max_genome >= (1 << 28)) {
         err = std::string(who) + ": unsupported build options (genome_batch_size in [1, 2^17], contig_interval >= 0, max_genome < 2^28)";
@@ -773,15 +798,33 @@ static bool build_opt_ok(const char *who, const lm_build_opt &bo, std::string &e
 }
 
 // What every front end begins with, ix->opt and ix->device being set: the stream, the HostIndex header, the mask set
-// (generated, or the masks of the index `bh` that is continued), pfx[f] = first mask of the p-base prefix f - every prefix
-// once or twice, which is what lets k_capture_g find the masks of a prefix without a table - and the upload of both.
+// (generated, the caller's `given`, or the masks of the index `bh` that is continued), checked by the one rule of
+// lm_mask_plan.h, pfx[f] = first mask of the p-base prefix f, and the upload of both.  `who`: the entry point, for the text.
 // LM_OK, or the status to return with its text in g_open_error.
-static lm_status builder_header(lm_index *ix, int K, int M, int64_t mask_seed, int contig_interval, const HostIndex *bh, std::vector<int32_t> &pfx) {
+static lm_status builder_header(const char *who, lm_index *ix, int K, int M, int64_t mask_seed, int contig_interval, const HostIndex *bh,
+                                const uint64_t *given, std::vector<int32_t> &pfx) {
+    HostIndex &h = ix->host;
+    // (the masks first: a set that is refused costs no device work)
+    if (bh) h.masks = bh->masks;
+    else if (given) h.masks.assign(given, given + M);
+    else gen_masks(K, M, (uint64_t)mask_seed, h.masks);
+    MaskPlan mp;
+    {
+        std::string why;
+        if (!plan_masks(K, h.masks.data(), h.masks.size(), mp, why)) {
+            g_open_error = std::string(who) + ": the mask set cannot be built with: " + why;
+            return LM_ERR_ARG;
+        }
+    }
+    if (bh && bh->mask_prefix != mp.p) {
+        g_open_error = std::string(who) + ": the index carries a mask prefix of " + std::to_string(bh->mask_prefix) + " bases, its " + std::to_string(M) +
+                       " masks give " + std::to_string(mp.p);
+        return LM_ERR_ARG;
+    }
     HIPCHK(hipSetDevice(ix->device));
     HIPCHK(hipStreamCreate(&ix->lane[0].main.st));
     const lm_options &opt = ix->opt;
-    HostIndex &h = ix->host;
-    const int p = bh ? bh->mask_prefix : mask_prefix_of(M);
+    const int p = mp.p;
     h.k = K;
     h.M = M;
     h.main_version = 3;
@@ -800,17 +843,7 @@ static lm_status builder_header(lm_index *ix, int K, int M, int64_t mask_seed, i
         g_open_error = "MinPrefix out of range for this index";
         return LM_ERR_OPTION;
     }
-    if (bh) h.masks = bh->masks;
-    else gen_masks(K, M, (uint64_t)mask_seed, h.masks);
-    pfx.assign((size_t)(1ull << (2 * p)) + 1, 0);
-    for (int i = 0; i < M; i++) pfx[(size_t)(h.masks[(size_t)i] >> ((K - p) << 1)) + 1]++;
-    for (size_t i = 1; i < pfx.size(); i++) {
-        if (pfx[i] < 1 || pfx[i] > 2) {
-            g_open_error = "index build: the mask set does not have every " + std::to_string(p) + "-base prefix once or twice";
-            return LM_ERR_ARG;
-        }
-        pfx[i] += pfx[i - 1];
-    }
+    pfx = std::move(mp.pfx_first);
     ix->d_masks.ensure((size_t)M);
     ix->d_pfx_first.ensure(pfx.size());
     HIPCHK(hipMemcpyAsync(ix->d_masks.p, h.masks.data(), (size_t)M * 8, hipMemcpyHostToDevice, ix->lane[0].main.st));
@@ -902,23 +935,41 @@ static void build_seed_index(lm_index *ix, const std::vector<int32_t> &pfx, cons
     v.g2local = h.g2local.empty() ? nullptr : ix->d_g2local.p;
     const MaskTab mt{ix->d_masks.p, ix->d_pfx_first.p, K, p, M};
     const GenomeTab gt{ix->d_g_off.p, ix->d_g_len.p, ix->d_g_bg.p, d_reg_off.p, d_reg_s.p, d_reg_e.p};
-    // ---- prefix -> masks without a table in memory (k_capture_g): every prefix once or twice (checked by builder_header)
+    // ---- prefix -> masks (k_capture_g).  Every prefix once or twice (every generated set, and a caller's set of that shape):
+    // without a table in memory, from the doubled-prefix map.  Otherwise (builder_header checked the set: up to 32 masks on a
+    // prefix) from the prefix table the handle carries, ix->d_pfx_first.
     const int npfx = 1 << (2 * p), nwords = (npfx + 63) >> 6;
     std::vector<uint64_t> dmap((size_t)nwords, 0);
     std::vector<uint32_t> dcnt((size_t)nwords, 0);
-    for (int f = 0; f < npfx; f++)
-        if (pfx[(size_t)f + 1] - pfx[(size_t)f] == 2) dmap[(size_t)(f >> 6)] |= 1ull << (f & 63);
+    bool csr = false;
+    for (int f = 0; f < npfx; f++) {
+        const int n = pfx[(size_t)f + 1] - pfx[(size_t)f];
+        if (n == 2) dmap[(size_t)(f >> 6)] |= 1ull << (f & 63);
+        if (n < 1 || n > 2) csr = true;
+    }
     for (int w = 1; w < nwords; w++) dcnt[(size_t)w] = dcnt[(size_t)w - 1] + (uint32_t)__builtin_popcountll(dmap[(size_t)w - 1]);
-    // capture in LDS when the per-mask minima fit a CU's LDS, otherwise minima in a global table
+    // capture in LDS when the per-mask minima fit a CU's LDS, otherwise minima in a global table (one threshold for both ways
+    // to find the masks of a prefix).  The prefix table of the CSR instantiations is staged in LDS where it fits beside them:
+    // always for p <= 6 (16 KB at most, under 16384 x 8 B of minima) and for p = 7 with the minima in a global table (64 KB on
+    // its own); with p = 7 and the minima in LDS (16384 .. ~20000 masks: 128 .. 160 KB) it cannot, and is read from global
+    // memory.  LM_BUILD_PFX_GLOBAL (measurement only; results do not depend on it) keeps it there always.
     const size_t lds_full = (size_t)M * 8 + (size_t)nwords * 12 + 64;
     const bool lds_capture = lds_full <= 160 * 1024;
-    const size_t lds_bytes = lds_capture ? lds_full : (size_t)nwords * 12 + 64;
+    const size_t csr_base = (lds_capture ? (size_t)M * 8 : 0) + 64, csr_tab = ((size_t)npfx + 1) * 4;
+    const bool tab_lds = csr && csr_base + csr_tab + 16 <= 160 * 1024 && getenv("LM_BUILD_PFX_GLOBAL") == nullptr;
+    const size_t lds_bytes = csr ? csr_base + (tab_lds ? csr_tab : 0) : lds_capture ? lds_full : (size_t)nwords * 12 + 64;
     DBuf<uint64_t> dbl_map;
     DBuf<uint32_t> dbl_cnt;
     copy_up(dbl_map, dmap);
     copy_up(dbl_cnt, dcnt);
-    if (lds_capture && lds_bytes > 64 * 1024)
-        HIPCHK(hipFuncSetAttribute((const void *)k_capture_g<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    using CaptureKernel = decltype(&k_capture_g<true, false, false>);
+    const CaptureKernel capture = !csr ? (lds_capture ? k_capture_g<true, false, false> : k_capture_g<false, false, false>)
+                                  : lds_capture ? (tab_lds ? k_capture_g<true, true, true> : k_capture_g<true, true, false>)
+                                                : (tab_lds ? k_capture_g<false, true, true> : k_capture_g<false, true, false>);
+    if (lds_bytes > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *)capture, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    if (dbg)
+        fprintf(stderr, "[lm] builder: capture with the minima in %s, the masks of a prefix from %s\n", lds_capture ? "LDS" : "a global table",
+                !csr ? "the doubled-prefix map" : tab_lds ? "the prefix table in LDS" : "the prefix table in global memory");
     // ---- chunks of records within the caller's limits (and 192 MB of minima where they live in a global table); the staging
     // arrays are sized from the largest chunk with one estimate per record
     const int64_t ch_max = std::max<int64_t>(1, lds_capture ? chunk_records : std::min<int64_t>(chunk_records, ((int64_t)192 << 20) / ((int64_t)M * 8)));
@@ -1005,12 +1056,9 @@ static void build_seed_index(lm_index *ix, const std::vector<int32_t> &pfx, cons
         const unsigned long long pos_lim = pos_cap - (unsigned long long)c.n - 1;
         const double ta = now_ms();
         HIPCHK(hipMemsetAsync(counters.p, 0, 2 * sizeof(unsigned long long), st));
-        if (lds_capture)
-            hipLaunchKernelGGL(k_capture_g<true>, dim3(c.n), dim3(1024), lds_bytes, st, gt, mt, ix->d_gbits.p, c.l0, dbl_map.p, dbl_cnt.p,
-                               hashes.p, miss_pos.p, miss_cnt.p, s_mask.p, s_kmer.p, s_val.p, counters.p, cap, pos_keys.p, counters.p + 1, pos_lim, dbg ? counters.p + 4 : nullptr);
-        else
-            hipLaunchKernelGGL(k_capture_g<false>, dim3(c.n), dim3(1024), lds_bytes, st, gt, mt, ix->d_gbits.p, c.l0, dbl_map.p, dbl_cnt.p,
-                               hashes.p, miss_pos.p, miss_cnt.p, s_mask.p, s_kmer.p, s_val.p, counters.p, cap, pos_keys.p, counters.p + 1, pos_lim, dbg ? counters.p + 4 : nullptr);
+        hipLaunchKernelGGL(capture, dim3(c.n), dim3(1024), lds_bytes, st, gt, mt, ix->d_gbits.p, c.l0, dbl_map.p, dbl_cnt.p, hashes.p,
+                           miss_pos.p, miss_cnt.p, s_mask.p, s_kmer.p, s_val.p, counters.p, cap, pos_keys.p, counters.p + 1, pos_lim,
+                           dbg ? (unsigned long long *)(counters.p + 4) : nullptr);
         HIPCHK(hipGetLastError());
         unsigned long long hc[8];
         HIPCHK(hipMemcpyAsync(hc, counters.p, sizeof hc, hipMemcpyDeviceToHost, st));
@@ -1030,8 +1078,13 @@ static void build_seed_index(lm_index *ix, const std::vector<int32_t> &pfx, cons
         hipLaunchKernelGGL(k_pseudo_pos_g, dim3((c.n + 63) / 64), dim3(64), 0, st, gt, c.l0, c.n, K, pos_keys.p, npk);
         npk += (unsigned long long)c.n;
         prim_sort_keys(st, ix->lane[0].main.tmp, pos_keys.p, pos_keys2.p, (size_t)npk, 0, 64);
-        hipLaunchKernelGGL(k_desert_fill_g, dim3(gridn(((int64_t)npk + 63) / 64, 4)), dim3(256), 0, st, gt, mt, ix->d_gbits.p, c.l0,
-                           pos_keys2.p, (int64_t)npk, max_desert, seed_dist, s_mask.p, s_kmer.p, s_val.p, counters.p, cap);
+        // A wavefront walks the deserts among its seed pairs one after the other.  64 pairs each where there are pairs enough to
+        // fill the device that way (any set of the usual mask counts); fewer where there are not - a record set under a few dozen
+        // masks has a few hundred pairs, nearly all of them deserts of thousands of bases whose every candidate fails its window
+        // sweep, and five wavefronts walking 64 of those each take a minute where one wavefront per desert takes a second
+        const int ppw = (int)std::max<int64_t>(1, std::min<int64_t>(64, (int64_t)npk / 8192));
+        hipLaunchKernelGGL(k_desert_fill_g, dim3(gridn(((int64_t)npk + ppw - 1) / ppw, 4)), dim3(256), 0, st, gt, mt, ix->d_gbits.p, c.l0,
+                           pos_keys2.p, (int64_t)npk, ppw, max_desert, seed_dist, s_mask.p, s_kmer.p, s_val.p, counters.p, cap);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(hc, counters.p, sizeof hc, hipMemcpyDeviceToHost, st));
         bsync(ix);
@@ -1274,11 +1327,14 @@ void lm_build_opt_default(lm_build_opt *o) {
     o->max_genome = 20000000;    // index.go:538
 }
 
-lm_status lm_index_builder_new(const lm_build_opt *bo, const lm_options *opt, const lm_residency *res, int device, lm_index_builder **out) {
+// lm_index_builder_new (masks == nullptr: the generated set of bo->masks masks from bo->mask_seed) and
+// lm_index_builder_new_masks (the caller's set: nmasks rules, bo->masks is ignored, bo->mask_seed is only carried to info.toml)
+static lm_status builder_new(const char *who, const lm_build_opt *bo_in, const uint64_t *masks, size_t nmasks, const lm_options *opt,
+                             const lm_residency *res, int device, lm_index_builder **out) {
     if (!out) return LM_ERR_ARG;
     *out = nullptr;
-    if (!bo || !opt) {
-        g_open_error = "lm_index_builder_new: build options and search options are needed";
+    if (!bo_in || !opt) {
+        g_open_error = std::string(who) + ": build options and search options are needed";
         return LM_ERR_ARG;
     }
     lm_res_request rq;
@@ -1286,7 +1342,19 @@ lm_status lm_index_builder_new(const lm_build_opt *bo, const lm_options *opt, co
         const lm_status rs = lm_res_resolve(res, rq, g_open_error);
         if (rs != LM_OK) return rs;
     }
-    if (!build_opt_ok("lm_index_builder_new", *bo, g_open_error)) return LM_ERR_ARG;
+    lm_build_opt bo_copy = *bo_in;
+    if (masks) {
+        // (the set by the mask rule's own text, before the count is narrowed to the int of lm_build_opt and before any device is asked for)
+        MaskPlan mp;
+        std::string why;
+        if (!plan_masks(bo_in->k, masks, nmasks, mp, why)) {
+            g_open_error = std::string(who) + ": the mask set cannot be built with: " + why;
+            return LM_ERR_ARG;
+        }
+        bo_copy.masks = (int32_t)nmasks;
+    }
+    const lm_build_opt *bo = &bo_copy;
+    if (!build_opt_ok(who, *bo, masks == nullptr, g_open_error)) return LM_ERR_ARG;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
         (void)hipGetLastError();
@@ -1303,7 +1371,7 @@ lm_status lm_index_builder_new(const lm_build_opt *bo, const lm_options *opt, co
         b->ix = ix;
         ix->opt = *opt;
         ix->device = device;
-        const lm_status hs = builder_header(ix, bo->k, bo->masks, bo->mask_seed, bo->contig_interval, nullptr, b->pfx);
+        const lm_status hs = builder_header(who, ix, bo->k, bo->masks, bo->mask_seed, bo->contig_interval, nullptr, masks, b->pfx);
         if (hs != LM_OK) return hs;
     } catch (const std::exception &e) {
         g_open_error = e.what();
@@ -1311,6 +1379,18 @@ lm_status lm_index_builder_new(const lm_build_opt *bo, const lm_options *opt, co
     }
     *out = b.release();
     return LM_OK;
+}
+lm_status lm_index_builder_new(const lm_build_opt *bo, const lm_options *opt, const lm_residency *res, int device, lm_index_builder **out) {
+    return builder_new("lm_index_builder_new", bo, nullptr, 0, opt, res, device, out);
+}
+lm_status lm_index_builder_new_masks(const lm_build_opt *bo, const uint64_t *masks, size_t nmasks, const lm_options *opt, const lm_residency *res,
+                                     int device, lm_index_builder **out) {
+    if (!masks) {
+        if (out) *out = nullptr;
+        g_open_error = "lm_index_builder_new_masks: a mask set is needed";
+        return LM_ERR_ARG;
+    }
+    return builder_new("lm_index_builder_new_masks", bo, masks, nmasks, opt, res, device, out);
 }
 // A builder that continues a resident index ("Adding genomes to a resident index").  Everything per record -
 // key, captures, desert seeds, reversed seeds - is a function of the record and its number alone, and the packer takes seeds
@@ -1356,7 +1436,7 @@ static lm_status builder_from_model(const char *who, lm_index *base, bool contin
     bo.mask_seed = bh.rand_seed; // (the masks are the base's, whatever seed made them)
     bo.contig_interval = bh.contig_interval;
     bo.genome_batch_size = bh.genome_batch_size;
-    if (!build_opt_ok(who, bo, g_open_error)) return LM_ERR_ARG;
+    if (!build_opt_ok(who, bo, false, g_open_error)) return LM_ERR_ARG; // (the masks are the index's own: any k and shape the rule accepts)
     int64_t base_records = 0, nbase = 0;
     if (continued) {
         if (bh.synthetic && bh.shard_count > 1) {
@@ -1398,7 +1478,7 @@ static lm_status builder_from_model(const char *who, lm_index *base, bool contin
         b->ix = ix;
         ix->opt = base->opt;
         ix->device = base->device;
-        const lm_status hs = builder_header(ix, bh.k, bh.M, bh.rand_seed, bh.contig_interval, &bh, b->pfx);
+        const lm_status hs = builder_header(who, ix, bh.k, bh.M, bh.rand_seed, bh.contig_interval, &bh, nullptr, b->pfx);
         if (hs != LM_OK) return hs;
         HostIndex &h = ix->host;
         h.rand_seed = bh.rand_seed;
@@ -1677,7 +1757,7 @@ lm_status lm_index_build_synthetic_ex(const lm_synth_spec *spec, const lm_option
         g_open_error = "no HIP device available (this library has no CPU path)";
         return LM_ERR_NO_DEVICE;
     }
-    if (!seed_settings_ok("lm_index_build_synthetic", spec->k, spec->masks, spec->max_desert, spec->seed_dist, g_open_error)) return LM_ERR_ARG;
+    if (!seed_settings_ok("lm_index_build_synthetic", spec->k, spec->masks, spec->max_desert, spec->seed_dist, true, g_open_error)) return LM_ERR_ARG;
     if (spec->genome_len < 64 || spec->genomes < 1 || spec->genome_len >= (1 << 28) || spec->families < 1) {
         g_open_error = "lm_index_build_synthetic: unsupported spec (genome_len in [64, 2^28), genomes and families >= 1)";
         return LM_ERR_ARG;
@@ -1687,7 +1767,7 @@ lm_status lm_index_build_synthetic_ex(const lm_synth_spec *spec, const lm_option
         ix->opt = *opt;
         ix->device = device;
         std::vector<int32_t> pfx;
-        const lm_status hs = builder_header(ix, spec->k, spec->masks, spec->mask_seed, 1000, nullptr, pfx);
+        const lm_status hs = builder_header("lm_index_build_synthetic", ix, spec->k, spec->masks, spec->mask_seed, 1000, nullptr, nullptr, pfx);
         if (hs != LM_OK) {
             delete ix;
             return hs;

@@ -461,6 +461,15 @@ struct lm_qbatch {
     int64_t total_len = 0, total_pos = 0;
     DBuf<uint8_t> d_seq;
     DBuf<int64_t> d_qoff, d_posoff, d_segoff;
+    // The comparison k-mers of the pseudo-alignment are 31-mers whatever the index's k (SeqComparatorOptions.K, search.go:361):
+    // with k = 31 they share the positions above; with any other k they get position offsets of their own (cmp_split)
+    bool cmp_split = false;
+    std::vector<int64_t> h_posoff_cmp;
+    int64_t total_pos_cmp = 0;
+    DBuf<int64_t> d_posoff_cmp, d_segoff_cmp;
+    const int64_t *posoff_cmp() const { return cmp_split ? d_posoff_cmp.p : d_posoff.p; }
+    const int64_t *segoff_cmp() const { return cmp_split ? d_segoff_cmp.p : d_segoff.p; }
+    int64_t npos_cmp() const { return cmp_split ? total_pos_cmp : total_pos; }
     // per-query prefix filter of the pseudo-alignment (k_build_cmp_bits): 2^bits_log[q] bits at word bits_off[q]
     DBuf<int64_t> d_bits_off;
     DBuf<int32_t> d_bits_log;
@@ -569,11 +578,14 @@ struct Work {
     }
 };
 
+// SeqComparatorOptions.K (search.go:361): the pseudo-alignment indexes and compares 31-mers, whatever k the seed index has
+static const int LM_CMP_K = 31;
 static void stage_kmers(Work &w) {
     lm_index *ix = w.ix;
     lm_qbatch *qb = w.qb;
     int64_t P = qb->total_pos;
-    size_t n2 = (size_t)std::max<int64_t>(2 * P, 1);
+    const int64_t PC = qb->npos_cmp();
+    size_t n2 = (size_t)std::max<int64_t>(2 * std::max(P, PC), 1);
     w.keys_all.ensure(n2);
     w.keys_all2.ensure(n2);
     w.keys_cmp.ensure(n2);
@@ -588,30 +600,41 @@ static void stage_kmers(Work &w) {
     w.v_all = w.vals_all.p;
     w.k_cmp = w.keys_cmp.p;
     w.v_cmp = w.vals_cmp.p;
-    if (P == 0) return;
+    if (P == 0 && PC == 0) return;
     {
         Prof p(ix, "k_extract_kmers", qb->total_len + 2 * P * 24);
-        launch_extract_kmers(S(ix), qb->d_seq.p, qb->d_qoff.p, qb->d_posoff.p, qb->nq, ix->host.k, P, w.keys_all.p,
-                             w.vals_all.p, w.keys_cmp.p, w.vals_cmp.p, w.nvalid.p);
+        if (P > 0)
+            launch_extract_kmers(S(ix), qb->d_seq.p, qb->d_qoff.p, qb->d_posoff.p, qb->nq, ix->host.k, P, w.keys_all.p,
+                                 w.vals_all.p, w.keys_cmp.p, w.vals_cmp.p, w.nvalid.p);
+        if (qb->cmp_split) {
+            // a second pass for the 31-mers of the comparison index; the first one's comparison outputs and counts are
+            // overwritten, this one's k-mers of the index's kind go to the sort's second buffers, which are free until the sort
+            HIPCHK(hipMemsetAsync(w.nvalid.p, 0, sizeof(int32_t) * (qb->nq + 1), S(ix)));
+            if (PC > 0)
+                launch_extract_kmers(S(ix), qb->d_seq.p, qb->d_qoff.p, qb->d_posoff_cmp.p, qb->nq, LM_CMP_K, PC, w.keys_cmp2.p,
+                                     w.vals_cmp2.p, w.keys_cmp.p, w.vals_cmp.p, w.nvalid.p);
+        }
     }
     {
         Prof p(ix, "segmented_sort_kmers", 2 * (2 * P) * 24); // two sorts of 2P (u64 key, u32 value) pairs, in and out
         int end_bit = std::min(64, 2 * ix->host.k);
-        prim_segmented_sort_pairs(S(ix), TMP(ix), w.keys_all.p, w.keys_all2.p, w.vals_all.p, w.vals_all2.p, (size_t)(2 * P),
-                                  (size_t)qb->nq, qb->d_segoff.p, 0, end_bit);
-        prim_segmented_sort_pairs(S(ix), TMP(ix), w.keys_cmp.p, w.keys_cmp2.p, w.vals_cmp.p, w.vals_cmp2.p, (size_t)(2 * P),
-                                  (size_t)qb->nq, qb->d_segoff.p, 0, 64);
+        if (P > 0)
+            prim_segmented_sort_pairs(S(ix), TMP(ix), w.keys_all.p, w.keys_all2.p, w.vals_all.p, w.vals_all2.p, (size_t)(2 * P),
+                                      (size_t)qb->nq, qb->d_segoff.p, 0, end_bit);
+        if (PC > 0)
+            prim_segmented_sort_pairs(S(ix), TMP(ix), w.keys_cmp.p, w.keys_cmp2.p, w.vals_cmp.p, w.vals_cmp2.p, (size_t)(2 * PC),
+                                      (size_t)qb->nq, qb->segoff_cmp(), 0, 64);
     }
     w.k_all = w.keys_all2.p;
     w.v_all = w.vals_all2.p;
     w.k_cmp = w.keys_cmp2.p;
     w.v_cmp = w.vals_cmp2.p;
     w.cmp_tab.ensure((size_t)qb->tab_words + 1);
-    launch_build_cmp_tab(S(ix), w.k_cmp, qb->d_posoff.p, w.nvalid.p, qb->nq, ix->host.k, qb->d_tab_off.p, qb->d_tab_bits.p,
+    launch_build_cmp_tab(S(ix), w.k_cmp, qb->posoff_cmp(), w.nvalid.p, qb->nq, LM_CMP_K, qb->d_tab_off.p, qb->d_tab_bits.p,
                          qb->tab_words, w.cmp_tab.p);
     w.cmp_bits.ensure((size_t)qb->bits_words + 1);
     HIPCHK(hipMemsetAsync(w.cmp_bits.p, 0, (size_t)qb->bits_words * sizeof(uint32_t), S(ix)));
-    launch_build_cmp_bits(S(ix), w.k_cmp, qb->d_posoff.p, w.nvalid.p, qb->nq, ix->host.k, qb->d_bits_off.p, qb->d_bits_log.p,
+    launch_build_cmp_bits(S(ix), w.k_cmp, qb->posoff_cmp(), w.nvalid.p, qb->nq, LM_CMP_K, qb->d_bits_off.p, qb->d_bits_log.p,
                           w.cmp_bits.p);
 }
 
@@ -1560,6 +1583,18 @@ static lm_qbatch *upload_part(lm_index *ix, const lm_query *queries, size_t nq, 
             if (queries[i].len) memcpy(&qb->h_seq[(size_t)qb->h_qoff[i]], queries[i].seq, queries[i].len);
         std::vector<int64_t> segoff(nq + 1);
         for (size_t i = 0; i <= nq; i++) segoff[i] = 2 * qb->h_posoff[i];
+        qb->cmp_split = K != LM_CMP_K;
+        if (qb->cmp_split) {
+            qb->h_posoff_cmp.assign(nq + 1, 0);
+            for (size_t i = 0; i < nq; i++)
+                qb->h_posoff_cmp[i + 1] = qb->h_posoff_cmp[i] + std::max<int64_t>((int64_t)queries[i].len - LM_CMP_K + 1, 0);
+            qb->total_pos_cmp = qb->h_posoff_cmp[nq];
+            std::vector<int64_t> segoff_cmp(nq + 1);
+            for (size_t i = 0; i <= nq; i++) segoff_cmp[i] = 2 * qb->h_posoff_cmp[i];
+            h2d(ix, qb->d_posoff_cmp, qb->h_posoff_cmp);
+            h2d(ix, qb->d_segoff_cmp, segoff_cmp);
+        }
+        const std::vector<int64_t> &pc = qb->cmp_split ? qb->h_posoff_cmp : qb->h_posoff; // (the filters and tables below are the comparison's)
         h2d(ix, qb->d_seq, qb->h_seq);
         h2d(ix, qb->d_qoff, qb->h_qoff);
         h2d(ix, qb->d_posoff, qb->h_posoff);
@@ -1569,7 +1604,7 @@ static lm_qbatch *upload_part(lm_index *ix, const lm_query *queries, size_t nq, 
             std::vector<int64_t> boff(nq + 1, 0);
             std::vector<int32_t> blog(nq + 1, 13);
             for (size_t i = 0; i < nq; i++) {
-                const int64_t nk = 2 * (qb->h_posoff[i + 1] - qb->h_posoff[i]);
+                const int64_t nk = 2 * (pc[i + 1] - pc[i]);
                 int lg = 13;
                 while (lg < 24 && ((int64_t)1 << lg) < 16 * nk) lg++;
                 blog[i] = lg;
@@ -1579,7 +1614,7 @@ static lm_qbatch *upload_part(lm_index *ix, const lm_query *queries, size_t nq, 
             std::vector<int64_t> toff(nq + 1, 0);
             std::vector<int32_t> tbits(nq + 1, LM_TAB_BITS_MIN);
             for (size_t i = 0; i < nq; i++) { // about two buckets per k-mer
-                const int64_t nk = 2 * (qb->h_posoff[i + 1] - qb->h_posoff[i]);
+                const int64_t nk = 2 * (pc[i + 1] - pc[i]);
                 int tb = LM_TAB_BITS_MIN;
                 while (tb < LM_TAB_BITS_MAX && ((int64_t)1 << tb) < 2 * nk) tb++;
                 tbits[i] = tb;
@@ -1952,14 +1987,14 @@ static void run_pseudo(AlignCtx &a, TaskSpan ht, std::vector<int64_t> &res_off_h
         HIPCHK(hipMemsetAsync(a.pa_count.p, 0, (size_t)(2 + nseg) * sizeof(unsigned long long), S(ix)));
         {
             Prof p(ix, "k_pa_filter", W);
-            launch_pa_filter(S(ix), ix->view, tasks_d, src_d, nt, a.wb, qb->d_posoff.p, a.w->nvalid.p, a.w->cmp_bits.p,
-                             qb->d_bits_off.p, qb->d_bits_log.p, ix->host.k, 11, a.pa_count.p + 2, nseg, seg_cap, a.B1.p,
+            launch_pa_filter(S(ix), ix->view, tasks_d, src_d, nt, a.wb, qb->posoff_cmp(), a.w->nvalid.p, a.w->cmp_bits.p,
+                             qb->d_bits_off.p, qb->d_bits_log.p, LM_CMP_K, 11, a.pa_count.p + 2, nseg, seg_cap, a.B1.p,
                              a.pa_count.p + 1, device_cus(ix->device), by_group ? 1 : 0, ix->tune.pa_filter_roll != 0);
         }
         {
             Prof p(ix, "k_pa_search");
-            launch_pa_search(S(ix), ix->view, tasks_d, src_d, a.wb, a.w->k_cmp, a.w->v_cmp, qb->d_posoff.p, a.w->nvalid.p,
-                             a.w->cmp_tab.p, qb->d_tab_off.p, qb->d_tab_bits.p, ix->host.k, 11, a.pa_count.p + 2, nseg, seg_cap,
+            launch_pa_search(S(ix), ix->view, tasks_d, src_d, a.wb, a.w->k_cmp, a.w->v_cmp, qb->posoff_cmp(), a.w->nvalid.p,
+                             a.w->cmp_tab.p, qb->d_tab_off.p, qb->d_tab_bits.p, LM_CMP_K, 11, a.pa_count.p + 2, nseg, seg_cap,
                              a.B1.p, a.pa_count.p, a.pa_cap, a.A0.p, a.B0.p, compact ? qbits : 0, compact ? tbits : 0,
                              by_group ? 1 : 0);
         }
@@ -1979,7 +2014,7 @@ static void run_pseudo(AlignCtx &a, TaskSpan ht, std::vector<int64_t> &res_off_h
             for (int64_t i = 0; i < nt; i++)
                 if (ht[i].q != prevq) { // tasks are in (query, genome) order
                     prevq = ht[i].q;
-                    idx += 24 * std::max<int64_t>(0, qb->h_qoff[prevq + 1] - qb->h_qoff[prevq] - (ix->host.k - 1));
+                    idx += 24 * std::max<int64_t>(0, qb->h_qoff[prevq + 1] - qb->h_qoff[prevq] - (LM_CMP_K - 1));
                 }
             prof_add_bytes(ix, "k_pa_search", 8 * std::min<int64_t>(ncand, a.pa_cap) + 8 * std::min<int64_t>(TP, a.pa_cap) + idx);
         }
@@ -2053,7 +2088,7 @@ static void run_pseudo(AlignCtx &a, TaskSpan ht, std::vector<int64_t> &res_off_h
         o2.heuristic_pident = 15;
         {
             Prof p(ix, "k_pa_chain", TP * 32);
-            launch_pa_chain(S(ix), a.B0.p, a.pa_off.p, nt, ix->host.k, o2, a.subs.p, a.marks.p, a.msi.p, a.stack.p,
+            launch_pa_chain(S(ix), a.B0.p, a.pa_off.p, nt, LM_CMP_K, o2, a.subs.p, a.marks.p, a.msi.p, a.stack.p,
                             a.out.p, a.out_n.p, a.clr_n.p, compact ? qbits : 0, compact ? tbits : 0);
         }
         a.res_off.ensure((size_t)nt + 2);
@@ -3509,6 +3544,8 @@ static void search_parts(lm_index *ix, lm_qbatch *qb, lm_result *res, const Sear
         qb->d_qoff.release();
         qb->d_posoff.release();
         qb->d_segoff.release();
+        qb->d_posoff_cmp.release();
+        qb->d_segoff_cmp.release();
     }
     struct PartState {
         lm_qbatch *part;
