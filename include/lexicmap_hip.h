@@ -317,6 +317,98 @@ size_t lm_seed_dist_records(const lm_seed_dist *sd, const lm_seed_dist_rec **rec
 size_t lm_seed_dist_hist(const lm_seed_dist *sd, const uint64_t **hist);
 size_t lm_seed_dist_rows(const lm_seed_dist *sd, const lm_seed_dist_row **rows);
 void lm_seed_dist_free(lm_seed_dist *sd);
+/* ---------------------------------------------------------------------------------------------------------
+ * Genome screening: which genomes of the index are closest to this assembly?  The first stage of `lexicmap genome search`,
+ * what -S/--only-genome-screening prints (GSearchScreen, lib-index-search-genome.go:114-543), for a batch of query genomes
+ * in one call, on the device (lexicmap_amd/csrc/lm_screen.hip; the rule and its deterministic choices: DESIGN.md section 11).
+ *   Query genome (search-genome-util.go:129-244): contigs pass the 2-bit base table (N and n become A BEFORE any gap is
+ *     looked for: a run of N is no skip region here, unlike in the builder) and are joined by k skipped bases; the skip
+ *     regions are exactly those spacers.  A query of fewer than k bases gives no rows.
+ *   Windows (:150-207): step = len / (windows + 1); window i is [i * step, i * step + 2 * step), the last one runs to len,
+ *     windows == 1 is the whole sequence.  Every window is masked on its own with the missing-prefix rule and - the
+ *     reference's behaviour, :180 - with the UNSHIFTED region list of the whole sequence.  Captures that are 0, CCC..,
+ *     GGG.., TTT.. or DUST > 50 are dropped; per mask the k-mers of all windows are de-duplicated.
+ *   Lookup (:371, kv-searcher2.go:326-549): every k-mer of mask m is range-searched in the forward list of m over
+ *     [kmer & ~low, kmer | low], low = 4^(k - min_prefix) - 1; every stored VALUE in range counts once with
+ *     Len = LCP(query k-mer, stored k-mer).  Values of genomes outside lm_index_set_genome_filter's whitelist count nowhere.
+ *     As in the reference, whose search starts from an anchor index in which a later run of k-mers with the same anchor bases
+ *     hides an earlier one (kv-reader.go:762-1021), a lookup returns nothing when the mask's list holds such a later run; only
+ *     lists with k-mers of other prefixes than their mask's (captures of tiny genomes) have one.
+ *   Per subject record (:316-341): score = sum of Len; with details, per mask Hits (saturating at 255) and Longest, and
+ *     from them hit_masks = #masks hit, hit_kmers = sum of Hits, score2 = sum of Longest, prefixes = Longest of the hit masks,
+ *     descending (search-genome.go:554-591).  details == 0: those fields are 0 and there are no prefixes.
+ *   Records of one split genome (:423-496) are one row: score summed over its hit records, the hit records' keys
+ *     ascending, details of the hit record with the LOWEST key (the reference takes whichever a Go map yields first).
+ *   Rows of a query (:498-509): score descending, ties by ascending lowest key (the reference: an unstable sort), cut to
+ *     top_n (0: all).  Rows are grouped by query in input order.  A sharded handle answers for its own records
+ *     (lm_index_screen_add_structure below makes its rows the unsharded index's rows for them).
+ * LM_ERR_ARG, text in lm_last_error(idx), handle still usable: windows < 1, nq > 0 with queries == NULL, a query without
+ * contigs, a query of 2^28 bases or more.  LM_ERR_OPTION: min_prefix outside [mask_prefix + anchor_prefix, k].
+ * LM_ERR_NOMEM (the text says what had to fit) when the (query, record, mask, Len) tuples of ONE mask do not fit beside
+ * the index: the tuples of a batch pass through the device in pieces of whole masks cut from a counting pass.
+ * LM_SCREEN_PIECE_TUPLES=<n> (tests and measurement only, read at call time) caps a piece at n tuples (or one mask's, when
+ * that is more), so that the multi-piece path runs on small input; no result depends on it.  opt == NULL: the defaults. */
+typedef struct lm_screen_opt {     /* lm_screen_opt_default(): the flag defaults of search-genome.go:729-739 */
+    int32_t min_prefix;            /* 21 */
+    int32_t windows;               /* 1 */
+    int32_t top_n;                 /* 10; 0 keeps all */
+    int32_t details;               /* 0 */
+} lm_screen_opt;
+typedef struct lm_genome_query {
+    const char *id;                /* not read by the screen: the printer's first column */
+    const lm_contig *contigs;
+    size_t ncontigs;
+} lm_genome_query;
+typedef struct lm_screen_row {
+    uint32_t query;                /* index into the batch */
+    uint32_t nkeys;                /* hit records of the genome: keys[keys_off .. keys_off + nkeys), ascending */
+    uint64_t score;
+    uint64_t batch_genome;         /* the lowest of those keys */
+    const char *genome_id;         /* borrowed from the index, valid until lm_index_close */
+    uint64_t keys_off;
+    uint64_t score2;
+    uint32_t hit_masks;            /* = number of prefixes: prefixes[prefixes_off .. prefixes_off + hit_masks) */
+    uint32_t pad;
+    uint64_t hit_kmers;
+    uint64_t prefixes_off;
+} lm_screen_row;
+typedef struct lm_screen_stats {   /* measured work of the call */
+    int64_t query_bases, windows, lookups, tuples, pieces; /* lookups: de-duplicated k-mers a list could match */
+    double ms_capture, ms_lookup, ms_reduce, ms_total;
+} lm_screen_stats;
+typedef struct lm_screen lm_screen;
+void lm_screen_opt_default(lm_screen_opt *o);
+lm_status lm_index_screen_genomes(lm_index *idx, const lm_genome_query *queries, size_t nq, const lm_screen_opt *opt, lm_screen **out);
+/* the accessors return the element count; any pointer may be NULL; valid until lm_screen_free */
+size_t lm_screen_rows(const lm_screen *s, const lm_screen_row **rows);
+size_t lm_screen_keys(const lm_screen *s, const uint64_t **keys);
+size_t lm_screen_prefixes(const lm_screen *s, const uint8_t **prefixes);
+void lm_screen_get_stats(const lm_screen *s, lm_screen_stats *stats);
+void lm_screen_free(lm_screen *s);
+/* Screening with shards.  The reference's anchor index (above) is a property of a mask's WHOLE list, and a shard holds the seeds
+ * of its own records only: left alone, a shard misses the hiding runs of other shards' records and its sums can exceed what the
+ * unsharded index gives for the same records.  lm_index_screen_structure exports what the rule reads of this handle's lists -
+ * per list a bitmap of the occupied partitions and the outlier k-mers, no values: 64 bits per 64 partitions and 8 B per outlier
+ * (*blob, *bytes; released with lm_free) - and lm_index_screen_add_structure adds another shard's to this handle.  Once every
+ * rank has added the structure of every other rank (the host carries the blobs, once per index), the rows of a rank are the
+ * unsharded index's rows for its records, and the union of all ranks' rows at top_n = 0 is the unsharded result.  blob == NULL
+ * or bytes == 0: back to the handle's own lists.  LM_ERR_ARG, the handle as it was: a blob of an index with other k, masks or
+ * partitions, a broken blob (wrong length, outlier offsets or k-mers of a list not ascending), a partition index of more than 6
+ * bases.  LM_ERR_NOMEM / LM_ERR_HIP while the union is put on the device: the handle is back to its own lists, never left with
+ * half a union.  The blob needs no alignment (it is copied out).  Its layout, all little-endian: uint64 magic; int32 k, masks,
+ * mask prefix, partition bases, W = words per list bitmap, 0; int64 outliers; uint64 bitmaps[2 * masks][W] (list 2 * mask +
+ * direction); int64 offsets[2 * masks + 1]; uint64 k-mers[outliers], ascending within a list.  The handle keeps the union on the
+ * host and on the device: 16 B per list and W word, 20 MB each at 20 000 masks, plus 8 B per outlier k-mer.
+ * These two calls go beyond what `lexicmap genome search` has: the reference has no shards. */
+lm_status lm_index_screen_structure(lm_index *idx, void **blob, size_t *bytes);
+lm_status lm_index_screen_add_structure(lm_index *idx, const void *blob, size_t bytes);
+/* One line of -S (search-genome.go:577-590; no newline): query id, subject id, minPrefix, fracMasks = hit_masks / masks,
+ * nMasks, sumPrefix = score2, avgPrefix = score2 / hit_masks as "%s\t%s\t%d\t%.4f\t%d\t%d\t%.2f", and with `extra` a tab and
+ * the comma-joined prefixes (`prefixes` = the array lm_screen_prefixes gives).  Returns the length that was / would be written. */
+int lm_format_screen_row(const lm_screen_row *row, const uint8_t *prefixes, const char *query_id, int min_prefix, int masks,
+                         int extra, char *buf, size_t buflen);
+/* the header line of -S (search-genome.go:482-486), no newline */
+const char *lm_screen_header(int extra);
 /* text of the last error on this handle, or of the last failed lm_index_open when idx == NULL */
 const char *lm_last_error(const lm_index *idx);
 

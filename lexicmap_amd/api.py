@@ -137,6 +137,25 @@ class SeedDistRow(C.Structure):
                 ("strand", C.c_uint32), ("dist", C.c_uint32)]
 
 
+class ScreenOpt(C.Structure):
+    _fields_ = [("min_prefix", C.c_int32), ("windows", C.c_int32), ("top_n", C.c_int32), ("details", C.c_int32)]
+
+
+class GenomeQuery(C.Structure):
+    _fields_ = [("id", C.c_char_p), ("contigs", C.POINTER(Contig)), ("ncontigs", C.c_size_t)]
+
+
+class ScreenRow(C.Structure):
+    _fields_ = [("query", C.c_uint32), ("nkeys", C.c_uint32), ("score", C.c_uint64), ("batch_genome", C.c_uint64),
+                ("genome_id", C.c_char_p), ("keys_off", C.c_uint64), ("score2", C.c_uint64), ("hit_masks", C.c_uint32),
+                ("pad", C.c_uint32), ("hit_kmers", C.c_uint64), ("prefixes_off", C.c_uint64)]
+
+
+class ScreenStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("query_bases", "windows", "lookups", "tuples", "pieces")] + \
+               [(n, C.c_double) for n in ("ms_capture", "ms_lookup", "ms_reduce", "ms_total")]
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char_p), ("launches", C.c_int64), ("total_ms", C.c_double), ("bytes", C.c_int64)]
 
@@ -236,6 +255,25 @@ def lib():
     L.lm_seed_dist_rows.restype = C.c_size_t
     L.lm_seed_dist_free.argtypes = [vp]
     L.lm_seed_dist_free.restype = None
+    L.lm_screen_opt_default.argtypes = [C.POINTER(ScreenOpt)]
+    L.lm_screen_opt_default.restype = None
+    L.lm_index_screen_genomes.argtypes = [vp, C.POINTER(GenomeQuery), C.c_size_t, C.POINTER(ScreenOpt), C.POINTER(vp)]
+    L.lm_screen_rows.argtypes = [vp, C.POINTER(C.POINTER(ScreenRow))]
+    L.lm_screen_rows.restype = C.c_size_t
+    L.lm_screen_keys.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint64))]
+    L.lm_screen_keys.restype = C.c_size_t
+    L.lm_screen_prefixes.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint8))]
+    L.lm_screen_prefixes.restype = C.c_size_t
+    L.lm_screen_get_stats.argtypes = [vp, C.POINTER(ScreenStats)]
+    L.lm_screen_get_stats.restype = None
+    L.lm_screen_free.argtypes = [vp]
+    L.lm_screen_free.restype = None
+    L.lm_format_screen_row.argtypes = [C.POINTER(ScreenRow), C.POINTER(C.c_uint8), C.c_char_p, C.c_int, C.c_int, C.c_int,
+                                       C.c_char_p, C.c_size_t]
+    L.lm_screen_header.argtypes = [C.c_int]
+    L.lm_screen_header.restype = C.c_char_p
+    L.lm_index_screen_structure.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.lm_index_screen_add_structure.argtypes = [vp, C.c_char_p, C.c_size_t]
     L.lm_index_fetch.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, C.c_char_p]
     L.lm_index_save.argtypes = [vp, C.c_char_p, C.c_int]
     L.lm_profile_enable.argtypes = [vp, C.c_int]
@@ -496,6 +534,75 @@ class Index:
                         rows=take(L.lm_seed_dist_rows, SeedDistRow, np.dtype(SeedDistRow)))
         finally:
             L.lm_seed_dist_free(sd)
+
+    def screen(self, genomes, min_prefix=21, windows=1, top_n=10, details=False, want_stats=False):
+        """lm_index_screen_genomes: which genomes of the index are closest to each query genome - the screening stage of
+        `lexicmap genome search` (-S), computed on the GPU.  genomes: [(genome_id, [(contig_id, seq bytes), ...]), ...] as
+        from_genomes takes them.  -> per query a list of rows (dicts) in output order: score, batch_genome (the lowest key),
+        genome_id, keys (the hit records of the genome, ascending: what set_genome_filter takes), and with details score2,
+        hit_masks, hit_kmers and prefixes (the longest match under every hit mask, descending); without details those are
+        0 and [].  top_n = 0 keeps all rows.  ValueError for what the library refuses as an argument or option (windows < 1,
+        a query without contigs or of 2^28 bases or more, min_prefix out of range).  want_stats: (rows, stats dict)."""
+        L = lib()
+        keep, qs = [], (GenomeQuery * max(len(genomes), 1))()
+        for i, (gid, contigs) in enumerate(genomes):
+            arr = (Contig * max(len(contigs), 1))()
+            for j, (cid, seq) in enumerate(contigs):
+                b = bytes(seq)
+                cb = cid if isinstance(cid, bytes) else str(cid).encode()
+                keep += [b, cb]
+                arr[j].id, arr[j].seq, arr[j].len = cb, b, len(b)
+            gb = gid if isinstance(gid, bytes) else str(gid).encode()
+            keep += [arr, gb]
+            qs[i].id, qs[i].contigs, qs[i].ncontigs = gb, arr, len(contigs)
+        opt = ScreenOpt(min_prefix, windows, top_n, 1 if details else 0)
+        sc = C.c_void_p()
+        st = L.lm_index_screen_genomes(self.h, qs, len(genomes), C.byref(opt), C.byref(sc))
+        if st in (3, 7):
+            raise ValueError(L.lm_last_error(self.h).decode())
+        if st != 0:
+            self._err(st)
+        try:
+            rows_p, keys_p, pref_p = C.POINTER(ScreenRow)(), C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint8)()
+            n = L.lm_screen_rows(sc, C.byref(rows_p))
+            L.lm_screen_keys(sc, C.byref(keys_p))
+            L.lm_screen_prefixes(sc, C.byref(pref_p))
+            out = [[] for _ in genomes]
+            for i in range(n):
+                r = rows_p[i]
+                d = {f[0]: getattr(r, f[0]) for f in ScreenRow._fields_ if f[0] not in ("pad", "keys_off", "prefixes_off", "nkeys")}
+                d["keys"] = [keys_p[r.keys_off + j] for j in range(r.nkeys)]
+                d["prefixes"] = list(C.string_at(C.addressof(pref_p.contents) + r.prefixes_off, r.hit_masks)) if r.hit_masks else []
+                out[r.query].append(d)
+            if not want_stats:
+                return out
+            stt = ScreenStats()
+            L.lm_screen_get_stats(sc, C.byref(stt))
+            return out, {f[0]: getattr(stt, f[0]) for f in ScreenStats._fields_}
+        finally:
+            L.lm_screen_free(sc)
+
+    def screen_structure(self):
+        """lm_index_screen_structure: what screening reads of this handle's lists beyond its own seeds (occupied partitions,
+        outlier k-mers) as bytes, for the other shards of the index"""
+        L = lib()
+        p, n = C.c_void_p(), C.c_size_t()
+        st = L.lm_index_screen_structure(self.h, C.byref(p), C.byref(n))
+        if st != 0:
+            self._err(st)
+        try:
+            return C.string_at(p, n.value)
+        finally:
+            L.lm_free(p)
+
+    def add_screen_structure(self, blob):
+        """lm_index_screen_add_structure: another shard's screen_structure(); once every shard has every other shard's,
+        screen() on a shard gives the unsharded index's rows for its records.  None: back to the handle's own lists."""
+        st = lib().lm_index_screen_add_structure(self.h, blob, len(blob) if blob else 0)
+        if st == 7:
+            raise ValueError(lib().lm_last_error(self.h).decode())
+        if st != 0:
+            self._err(st)
 
     def upload(self, seqs):
         arr, keep = _queries(seqs)
@@ -952,6 +1059,26 @@ def format_rows(rows, ids, lens, flags=0, want_text=True):
     out = C.string_at(text, n.value) if want_text else None
     L.lm_free(text)
     return (out if want_text else n.value), dt
+
+
+def format_screen_rows(rows, query_ids, min_prefix, masks, extra=False, header=False):
+    """the lines `lexicmap genome search -S` prints for the rows Index.screen returned (one list per query; query_ids their
+    ids), each formatted by lm_format_screen_row; header: lm_screen_header first.  masks: the index's mask count."""
+    L = lib()
+    out = [L.lm_screen_header(1 if extra else 0).decode()] if header else []
+    buf = C.create_string_buffer(1 << 20)
+    for qid, qrows in zip(query_ids, rows):
+        qb = qid if isinstance(qid, bytes) else str(qid).encode()
+        for d in qrows:
+            gid = d["genome_id"]
+            pref = (C.c_uint8 * max(len(d["prefixes"]), 1))(*d["prefixes"])
+            r = ScreenRow(0, len(d["keys"]), d["score"], d["batch_genome"], gid, 0, d["score2"], d["hit_masks"], 0, d["hit_kmers"], 0)
+            n = L.lm_format_screen_row(C.byref(r), pref, qb, min_prefix, masks, 1 if extra else 0, buf, len(buf))
+            if n >= len(buf):
+                buf = C.create_string_buffer(n + 1)
+                L.lm_format_screen_row(C.byref(r), pref, qb, min_prefix, masks, 1 if extra else 0, buf, len(buf))
+            out.append(buf.value.decode())
+    return out
 
 
 def row_names(rows, i):

@@ -345,7 +345,11 @@ template <bool LDS> __device__ __forceinline__ unsigned long long cap_min_load(c
     const int j0 = CSR ? pt[(pf)] : (int)((pf) + bc[(pf) >> 6] + (uint32_t)__popcll(w & ((1ull << ((pf) & 63)) - 1)));      \
     const int nj = CSR ? pt[(pf) + 1] - j0 : 1 + (int)((w >> ((pf) & 63)) & 1ull);
 // LDS of the CSR instantiations: the minima [M] (LDS), the wave totals of phase 2 [16], the prefix table [4^p + 1] (TLDS)
-template <bool LDS, bool CSR, bool TLDS>
+// KM = true (genome screening, lm_screen_capture): only the captured k-mer of every mask is wanted - the minimum xor its mask,
+// 0 where the record has no k-mer or the capture is of low complexity.  The launch ends after phase 1b and writes
+// s_kmer[block][M]; miss_pos / miss_cnt, the other staging arrays and the counters are not touched (null).  KM = false is the
+// kernel as it was: every added statement is under a compile-time `if (KM)`.
+template <bool LDS, bool CSR, bool TLDS, bool KM = false>
 __global__ __launch_bounds__(1024) void k_capture_g(GenomeTab gt, MaskTab mt, const uint8_t *__restrict__ gbits, int64_t l0,
                                                     const uint64_t *__restrict__ dbl_map, const uint32_t *__restrict__ dbl_cnt,
                                                     unsigned long long *__restrict__ ghash, uint32_t *__restrict__ miss_pos,
@@ -404,7 +408,7 @@ __global__ __launch_bounds__(1024) void k_capture_g(GenomeTab gt, MaskTab mt, co
         const int j = r0 + threadIdx.x;
         const bool miss = j < mt.M && cap_min_load<LDS>(&hs[j]) == ~0ull;
         if (!__any(miss)) {
-            if (j < mt.M) mp[j] = 0;
+            if (!KM && j < mt.M) mp[j] = 0;
             continue;
         }
         const unsigned long long mk = miss ? mt.masks[j] : 0ull;
@@ -441,14 +445,25 @@ __global__ __launch_bounds__(1024) void k_capture_g(GenomeTab gt, MaskTab mt, co
         }
         if (j < mt.M) {
             const bool got = miss && best != ~0ull;
-            mp[j] = got ? bcode + 1u : 0u;
-            mc[j] = got ? cnt : 0u;
+            if (!KM) {
+                mp[j] = got ? bcode + 1u : 0u;
+                mc[j] = got ? cnt : 0u;
+            }
             if (got) hs[j] = best;
         }
     }
     if (!LDS) __threadfence();
     __syncthreads();
     if (stamp) clk[2] = wall_clock64();
+    if (KM) {
+        for (int j = threadIdx.x; j < mt.M; j += blockDim.x) {
+            const unsigned long long hj = cap_min_load<LDS>(&hs[j]);
+            uint64_t x = hj == ~0ull ? 0ull : hj ^ mt.masks[j];
+            if (x != 0 && lm_low_complexity(x, mt.K)) x = 0;
+            s_kmer[(int64_t)c * mt.M + j] = x;
+        }
+        return;
+    }
     const uint64_t bg = gt.g_bg[l];
     // ---- phase 2: count, reserve ONE contiguous range of the staging arrays for the record (a per-capture atomic on the
     // shared counter costs more than the whole sweep), write
@@ -852,6 +867,50 @@ static lm_status builder_header(const char *who, lm_index *ix, int K, int M, int
     return LM_OK;
 }
 
+// How k_capture_g finds the masks of a prefix and where it keeps the minima, for a set of M masks with the prefix table pfx
+// (4^p + 1 entries): one decision for the builder and for genome screening.
+struct CapturePlan {
+    bool csr = false, lds_capture = false, tab_lds = false;
+    size_t lds_bytes = 0;
+    std::vector<uint64_t> dmap; // doubled-prefix map and per-word counts (CSR = false)
+    std::vector<uint32_t> dcnt;
+};
+static CapturePlan capture_plan(int M, int p, const std::vector<int32_t> &pfx) {
+    CapturePlan c;
+    const int npfx = 1 << (2 * p), nwords = (npfx + 63) >> 6;
+    std::vector<uint64_t> &dmap = c.dmap;
+    std::vector<uint32_t> &dcnt = c.dcnt;
+    dmap.assign((size_t)nwords, 0);
+    dcnt.assign((size_t)nwords, 0);
+    bool csr = false;
+    for (int f = 0; f < npfx; f++) {
+        const int n = pfx[(size_t)f + 1] - pfx[(size_t)f];
+        if (n == 2) dmap[(size_t)(f >> 6)] |= 1ull << (f & 63);
+        if (n < 1 || n > 2) csr = true;
+    }
+    for (int w = 1; w < nwords; w++) dcnt[(size_t)w] = dcnt[(size_t)w - 1] + (uint32_t)__builtin_popcountll(dmap[(size_t)w - 1]);
+    // capture in LDS when the per-mask minima fit a CU's LDS, otherwise minima in a global table (one threshold for both ways
+    // to find the masks of a prefix).  The prefix table of the CSR instantiations is staged in LDS where it fits beside them:
+    // always for p <= 6 (16 KB at most, under 16384 x 8 B of minima) and for p = 7 with the minima in a global table (64 KB on
+    // its own); with p = 7 and the minima in LDS (16384 .. ~20000 masks: 128 .. 160 KB) it cannot, and is read from global
+    // memory.  LM_BUILD_PFX_GLOBAL (measurement only, DESIGN.md section 11; results do not depend on it) keeps it there always.
+    const size_t lds_full = (size_t)M * 8 + (size_t)nwords * 12 + 64;
+    const bool lds_capture = lds_full <= 160 * 1024;
+    const size_t csr_base = (lds_capture ? (size_t)M * 8 : 0) + 64, csr_tab = ((size_t)npfx + 1) * 4;
+    const bool tab_lds = csr && csr_base + csr_tab + 16 <= 160 * 1024 && getenv("LM_BUILD_PFX_GLOBAL") == nullptr;
+    const size_t lds_bytes = csr ? csr_base + (tab_lds ? csr_tab : 0) : lds_capture ? lds_full : (size_t)nwords * 12 + 64;
+    c.csr = csr;
+    c.lds_capture = lds_capture;
+    c.tab_lds = tab_lds;
+    c.lds_bytes = lds_bytes;
+    return c;
+}
+template <bool KM> static decltype(&k_capture_g<true, false, false, KM>) capture_kernel(const CapturePlan &c) {
+    return !c.csr ? (c.lds_capture ? k_capture_g<true, false, false, KM> : k_capture_g<false, false, false, KM>)
+           : c.lds_capture ? (c.tab_lds ? k_capture_g<true, true, true, KM> : k_capture_g<true, true, false, KM>)
+                           : (c.tab_lds ? k_capture_g<false, true, true, KM> : k_capture_g<false, true, false, KM>);
+}
+
 // The seed pipeline, what every front end ends in.  In: the header and `pfx` of builder_header; the 2-bit store ix->d_gbits
 // with the records in slots of build_slot_bytes back to back, described by h.genomes (bits_off, len, bg); h.batch_first;
 // h.g2local where the records of a sharded set are numbered through a table.  It uploads the tables, fills in the view,
@@ -938,34 +997,15 @@ static void build_seed_index(lm_index *ix, const std::vector<int32_t> &pfx, cons
     // ---- prefix -> masks (k_capture_g).  Every prefix once or twice (every generated set, and a caller's set of that shape):
     // without a table in memory, from the doubled-prefix map.  Otherwise (builder_header checked the set: up to 32 masks on a
     // prefix) from the prefix table the handle carries, ix->d_pfx_first.
-    const int npfx = 1 << (2 * p), nwords = (npfx + 63) >> 6;
-    std::vector<uint64_t> dmap((size_t)nwords, 0);
-    std::vector<uint32_t> dcnt((size_t)nwords, 0);
-    bool csr = false;
-    for (int f = 0; f < npfx; f++) {
-        const int n = pfx[(size_t)f + 1] - pfx[(size_t)f];
-        if (n == 2) dmap[(size_t)(f >> 6)] |= 1ull << (f & 63);
-        if (n < 1 || n > 2) csr = true;
-    }
-    for (int w = 1; w < nwords; w++) dcnt[(size_t)w] = dcnt[(size_t)w - 1] + (uint32_t)__builtin_popcountll(dmap[(size_t)w - 1]);
-    // capture in LDS when the per-mask minima fit a CU's LDS, otherwise minima in a global table (one threshold for both ways
-    // to find the masks of a prefix).  The prefix table of the CSR instantiations is staged in LDS where it fits beside them:
-    // always for p <= 6 (16 KB at most, under 16384 x 8 B of minima) and for p = 7 with the minima in a global table (64 KB on
-    // its own); with p = 7 and the minima in LDS (16384 .. ~20000 masks: 128 .. 160 KB) it cannot, and is read from global
-    // memory.  LM_BUILD_PFX_GLOBAL (measurement only, DESIGN.md section 11; results do not depend on it) keeps it there always.
-    const size_t lds_full = (size_t)M * 8 + (size_t)nwords * 12 + 64;
-    const bool lds_capture = lds_full <= 160 * 1024;
-    const size_t csr_base = (lds_capture ? (size_t)M * 8 : 0) + 64, csr_tab = ((size_t)npfx + 1) * 4;
-    const bool tab_lds = csr && csr_base + csr_tab + 16 <= 160 * 1024 && getenv("LM_BUILD_PFX_GLOBAL") == nullptr;
-    const size_t lds_bytes = csr ? csr_base + (tab_lds ? csr_tab : 0) : lds_capture ? lds_full : (size_t)nwords * 12 + 64;
+    const CapturePlan cp = capture_plan(M, p, pfx);
+    const bool csr = cp.csr, lds_capture = cp.lds_capture, tab_lds = cp.tab_lds;
+    const size_t lds_bytes = cp.lds_bytes;
     DBuf<uint64_t> dbl_map;
     DBuf<uint32_t> dbl_cnt;
-    copy_up(dbl_map, dmap);
-    copy_up(dbl_cnt, dcnt);
+    copy_up(dbl_map, cp.dmap);
+    copy_up(dbl_cnt, cp.dcnt);
     using CaptureKernel = decltype(&k_capture_g<true, false, false>);
-    const CaptureKernel capture = !csr ? (lds_capture ? k_capture_g<true, false, false> : k_capture_g<false, false, false>)
-                                  : lds_capture ? (tab_lds ? k_capture_g<true, true, true> : k_capture_g<true, true, false>)
-                                                : (tab_lds ? k_capture_g<false, true, true> : k_capture_g<false, true, false>);
+    const CaptureKernel capture = capture_kernel<false>(cp);
     if (lds_bytes > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *)capture, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     if (dbg)
         fprintf(stderr, "[lm] builder: capture with the minima in %s, the masks of a prefix from %s\n", lds_capture ? "LDS" : "a global table",
@@ -1857,3 +1897,87 @@ lm_status lm_index_fetch(lm_index *ix, int64_t local_genome, int64_t start, int6
 }
 
 } // extern "C"
+
+// The window records of genome screening packed in ONE launch (k_pack_record packs one record of several contigs; here every
+// record is one stretch of `ascii` and there may be queries x windows of them): one lane per byte of the store, which finds its
+// record by the slot offsets goff (ascending, the slots back to back) and packs four bases with the builder's base table,
+// first base in bits 7-6.  Bytes behind a record's last base (the slot's padding) are left as they are: zero.
+namespace lm {
+__global__ void k_pack_windows(const uint8_t *__restrict__ ascii, const int64_t *__restrict__ src_off, const int64_t *__restrict__ goff,
+                               const int32_t *__restrict__ len, int64_t nrec, int64_t store, uint8_t *__restrict__ out) {
+    for (int64_t by = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; by < store; by += (int64_t)gridDim.x * blockDim.x) {
+        int64_t lo = 0, hi = nrec; // the last record whose slot starts at or before this byte
+        while (hi - lo > 1) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (goff[mid] <= by) lo = mid;
+            else hi = mid;
+        }
+        const int64_t i0 = (by - goff[lo]) << 2;
+        const int64_t n = len[lo];
+        if (i0 >= n) continue;
+        uint32_t v = 0;
+        for (int j = 0; j < 4; j++) v = (v << 2) | (i0 + j < n ? build_base_code(ascii[src_off[lo] + i0 + j]) : 0u);
+        out[by] = (uint8_t)v;
+    }
+}
+} // namespace lm
+
+// Genome screening's capture (lm_screen.hip), through the builder's store code and k_capture_g: "record" r is the window
+// ascii[src_off[r] .. + len[r]) of a query genome's concatenation (device memory), packed on its own by k_pack_windows so that
+// it starts on a slot boundary, and captured by one workgroup with the skip regions reg_s / reg_e [reg_off[r], reg_off[r + 1])
+// - in the window's own coordinates, whatever the caller means by them.  d_kmers[r * M + m] receives the k-mer mask m
+// captures in record r with the missing-prefix rule (check_shorter), 0 where there is none or it is of low complexity.  At
+// most 1024 records per launch: with the minima in a global table a record of a launch costs 8 B x masks of scratch.
+void lm::lm_screen_capture(lm_index *ix, hipStream_t st, const uint8_t *d_ascii, const std::vector<int64_t> &src_off,
+                           const std::vector<int32_t> &len, const std::vector<int32_t> &reg_off, const std::vector<int32_t> &reg_s,
+                           const std::vector<int32_t> &reg_e, uint64_t *d_kmers) {
+    const HostIndex &h = ix->host;
+    const int K = h.k, M = h.M, p = h.mask_prefix;
+    const int64_t nrec = (int64_t)len.size();
+    if (nrec == 0) return;
+    std::vector<int32_t> pfx(((size_t)1 << (2 * p)) + 1, 0);
+    for (int m = 0; m < M; m++) pfx[(size_t)(h.masks[(size_t)m] >> ((K - p) << 1)) + 1]++;
+    for (size_t f = 1; f < pfx.size(); f++) pfx[f] += pfx[f - 1];
+    const CapturePlan cp = capture_plan(M, p, pfx);
+    const auto capture = capture_kernel<true>(cp);
+    if (cp.lds_bytes > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *)capture, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cp.lds_bytes));
+    std::vector<int64_t> goff((size_t)nrec);
+    int64_t store = 0;
+    for (int64_t r = 0; r < nrec; r++) {
+        goff[(size_t)r] = store;
+        store += build_slot_bytes(len[(size_t)r]);
+    }
+    auto up = [&](auto &dbuf, const auto &vec) {
+        dbuf.alloc_exact(std::max<size_t>(vec.size(), 1));
+        if (!vec.empty()) HIPCHK(hipMemcpyAsync(dbuf.p, vec.data(), vec.size() * sizeof(vec[0]), hipMemcpyHostToDevice, st));
+    };
+    DBuf<uint8_t> bits;
+    DBuf<int64_t> d_goff, d_src;
+    DBuf<int32_t> d_len, d_reg_off, d_reg_s, d_reg_e;
+    DBuf<uint64_t> dbl_map;
+    DBuf<uint32_t> dbl_cnt;
+    DBuf<unsigned long long> hashes;
+    bits.alloc_exact((size_t)store, true, st);
+    up(d_goff, goff);
+    up(d_src, src_off);
+    up(d_len, len);
+    up(d_reg_off, reg_off);
+    up(d_reg_s, reg_s);
+    up(d_reg_e, reg_e);
+    up(dbl_map, cp.dmap);
+    up(dbl_cnt, cp.dcnt);
+    const int64_t per_launch = 1024;
+    hashes.alloc_exact(cp.lds_capture ? 1 : (size_t)std::min(nrec, per_launch) * M);
+    hipLaunchKernelGGL(k_pack_windows, dim3(gridn(store)), dim3(256), 0, st, d_ascii, d_src.p, d_goff.p, d_len.p, nrec, store, bits.p);
+    HIPCHK(hipGetLastError());
+    const MaskTab mt{ix->d_masks.p, ix->d_pfx_first.p, K, p, M};
+    const GenomeTab gt{d_goff.p, d_len.p, nullptr, d_reg_off.p, d_reg_s.p, d_reg_e.p};
+    for (int64_t r0 = 0; r0 < nrec; r0 += per_launch) {
+        const int n = (int)std::min(per_launch, nrec - r0);
+        hipLaunchKernelGGL(capture, dim3(n), dim3(1024), cp.lds_bytes, st, gt, mt, bits.p, r0, dbl_map.p, dbl_cnt.p, hashes.p, (uint32_t *)nullptr,
+                           (uint32_t *)nullptr, (uint16_t *)nullptr, d_kmers + r0 * M, (uint64_t *)nullptr, (unsigned long long *)nullptr, 0ull,
+                           (uint64_t *)nullptr, (unsigned long long *)nullptr, 0ull, (unsigned long long *)nullptr);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(st)); // (the tables and the store above go out of scope)
+}

@@ -459,6 +459,10 @@ struct SeedPacker {
 void sp_dump_range(const lm_index *src, hipStream_t st, const std::vector<int64_t> &off, bool flat, int64_t s0, int64_t s1,
                    uint16_t *s_mask, uint64_t *s_kmer, uint64_t *s_val, const uint64_t *new_bg = nullptr,
                    unsigned long long *n_out = nullptr);
+// the k-mer every mask captures in every window record of a batch of query genomes (lm_builder.hip, beside k_capture_g)
+void lm_screen_capture(lm_index *ix, hipStream_t st, const uint8_t *d_ascii, const std::vector<int64_t> &src_off,
+                       const std::vector<int32_t> &len, const std::vector<int32_t> &reg_off, const std::vector<int32_t> &reg_s,
+                       const std::vector<int32_t> &reg_e, uint64_t *d_kmers);
 } // namespace lm
 
 // Experiment / A-B switches of the kernels, read from the environment ONCE when the handle is created (a search never calls
@@ -532,6 +536,13 @@ struct lm_index {
         for (auto &sg : g_host_segs)
             if (sg.p) (void)hipHostFree(sg.p);
     }
+    // genome screening on a shard: the list structure of all shards (lm_index_screen_add_structure, lm_screen.hip)
+    bool sc_set = false;
+    int sc_W = 0;
+    std::vector<uint64_t> sc_bits, sc_kmers;
+    std::vector<int64_t> sc_off;
+    DBuf<uint64_t> d_sc_bits, d_sc_sum, d_sc_kmers;
+    DBuf<int64_t> d_sc_off;
     // scratch
     LaneSlabs lane_slabs;    // the two fixed slabs the lane arenas work in (LM_ARENA_RESERVE_PCT of the scratch budget)
     lm::Lane lane[2];        // lane 0's main stream and storage also serve the loader, the builder and every call outside a search (lm_index_close deletes work / actx first)

@@ -23,6 +23,7 @@
 
 #include "lm_algos.h"
 #include "lm_kernels.h"
+#include "lm_lookup_dev.h"
 
 namespace lm {
 
@@ -203,22 +204,7 @@ __device__ __forceinline__ int argmin_mask(const uint64_t *masks, const int32_t 
 // Lookups are compacted and sorted by (list, partition) so that neighbouring threads read neighbouring table entries
 // and partitions, and logical workgroups are laid out so that a contiguous eighth of the sorted lookups runs on one
 // XCD (each XCD has its own L2), see lookup_index().
-#define LM_LK_OUTLIER_BIT 31
-__device__ __forceinline__ int local_genome(const DevIndexView &ix, uint64_t bg) {
-    uint64_t batch = bg >> 17, gi = bg & 0x1ffff;
-    if (batch >= (uint64_t)ix.nbatches) return -1;
-    int64_t g = ix.batch_first[batch] + (int64_t)gi;
-    if (ix.g2local) return g < ix.batch_first[ix.nbatches] ? ix.g2local[g] : -1; // chunk-aware shard table (loader)
-    if (ix.shard_count > 1) {
-        if ((int)(g % ix.shard_count) != ix.shard_rank) return -1;
-        g /= ix.shard_count;
-    }
-    if (g >= ix.ngenomes) return -1;
-    return (int)g;
-}
-__device__ __forceinline__ bool genome_kept(const DevIndexView &ix, int64_t g) {
-    return g >= 0 && ((ix.g_keep[g >> 5] >> (g & 31)) & 1u) != 0;
-}
+// (LM_LK_OUTLIER_BIT, local_genome, genome_kept and lookup_range: lm_lookup_dev.h, shared with lm_screen.hip)
 __device__ __forceinline__ uint32_t lookup_sort_key(const DevIndexView &ix, uint32_t md, uint64_t x) {
     const int p = ix.mask_prefix;
     const uint64_t mp = ix.masks[md >> 1] >> ((ix.K - p) << 1);
@@ -304,15 +290,6 @@ __device__ __forceinline__ int64_t lookup_index(int64_t total) {
     const int64_t lb = (int64_t)(blockIdx.x & 7) * per + (int64_t)(blockIdx.x >> 3);
     const int64_t j = lb * blockDim.x + threadIdx.x;
     return j < total ? j : -1;
-}
-__device__ __forceinline__ void lookup_range(uint64_t key, int K, int min_prefix, uint64_t *left, uint64_t *right) {
-    if (min_prefix < K) {
-        const uint64_t low = (1ull << ((K - min_prefix) << 1)) - 1;
-        *left = key & ~low;
-        *right = key | low;
-    } else {
-        *left = *right = key;
-    }
 }
 __global__ __launch_bounds__(256) void k_lookup_count(DevIndexView ix, const uint64_t *__restrict__ kmers,
                                                       const int64_t *__restrict__ klo, const int64_t *__restrict__ khi,
