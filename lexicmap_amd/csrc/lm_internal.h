@@ -474,7 +474,7 @@ struct lm_tune {
     // LDS (0; impossible beyond 65 kb).  LM_WFA_FIRST_NC="2,2,4,8,8", LM_WFA_WIN="00101" override.
     int wfa_first_nc[LM_WFA_CLASSES] = {2, 2, 4, 8, 8};
     int wfa_win[LM_WFA_CLASSES] = {0, 0, 1, 0, 1};
-    int chain1_wave = 1;     // seed chaining of pairs with many anchors by a wavefront each
+    int chain1_wave = 1;     // seed chaining of pairs with many anchors by a wavefront each (k_chain1_wave); LM_CHAIN1_WAVE=0: every pair by one lane of k_chain1
     int pa_filter_roll = 1;  // k_pa_filter: a lane takes consecutive window positions (immediate funnel shifts over its own 64-base string); LM_PA_FILTER_ROLL=0: every 64th position, words passed between lanes
     int pa_seg_by_group = 1; // candidate segments by task group + XCD-local k_pa_search
     int wfa_resident_pct = 100; // share of the CUs' wavefront slots / LDS the persistent WFA kernels take (75 / 50 % measured in round 3: no gain / -20 %)
@@ -495,6 +495,7 @@ struct lm_tune {
             for (int c = 0; c < LM_WFA_CLASSES && e[c]; c++) wfa_win[c] = e[c] == '1';
         if (const char *e = getenv("LM_WFA_R16")) wfa_r16 = atoi(e) != 0;
         if (const char *e = getenv("LM_LOOKUP_FLAT")) lookup_flat = atoi(e) != 0;
+        if (const char *e = getenv("LM_CHAIN1_WAVE")) chain1_wave = atoi(e) != 0;
         if (const char *e = getenv("LM_TWO_LANES")) two_lanes = atoi(e) != 0;
         if (const char *e = getenv("LM_ARENA_RESERVE_PCT")) arena_reserve_pct = std::max(0, std::min(100, atoi(e)));
         if (const char *e = getenv("LM_PA_FILTER_ROLL")) pa_filter_roll = atoi(e) != 0;

@@ -39,6 +39,14 @@ struct DevIndexView {
     const int32_t *g2local;     // dense genome number -> local number (-1: other shard), or null: g % count == rank, g / count
 };
 
+// what the reference's start rule (screen_shadowed, lm_lookup_dev.h) reads of the lists of ALL shards; bits == null: the
+// handle's own lists are the index's
+struct ScreenShadowTab {
+    const uint64_t *bits, *sum, *kmers;
+    const int64_t *off;
+    int W;
+};
+
 struct Task { // one lexichash chain of one (query, genome): the pseudo-alignment problem
     uint32_t seg, q;
     int32_t g, rc;
@@ -96,7 +104,8 @@ void launch_lookup_prep(hipStream_t st, DevIndexView ix, const uint64_t *kmers, 
                         int64_t nqm, uint32_t *keys, uint32_t *slots, unsigned long long *counter);
 void launch_lookup_count(hipStream_t st, DevIndexView ix, const uint64_t *kmers, const int64_t *klo, const int64_t *khi,
                          const uint32_t *skeys, const uint32_t *sslots, int64_t nlk, int min_prefix, uint32_t *counts,
-                         int64_t *starts, int32_t *nscan, unsigned long long *stat_values, uint64_t *lkey, uint64_t *lrec);
+                         int64_t *starts, int32_t *nscan, unsigned long long *stat_values, uint64_t *lkey, uint64_t *lrec,
+                         ScreenShadowTab tab);
 // anchors with the lanes over the output (full-line stores, seeds read front to back); not under a genome whitelist
 void launch_lookup_emit_flat(hipStream_t st, DevIndexView ix, const uint32_t *vals_all, const uint32_t *skeys, const uint32_t *sslots,
                              int64_t nlk, const uint32_t *counts, const int64_t *offs, const int64_t *starts, const uint64_t *lkey,

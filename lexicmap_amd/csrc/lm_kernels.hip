@@ -204,7 +204,8 @@ __device__ __forceinline__ int argmin_mask(const uint64_t *masks, const int32_t 
 // Lookups are compacted and sorted by (list, partition) so that neighbouring threads read neighbouring table entries
 // and partitions, and logical workgroups are laid out so that a contiguous eighth of the sorted lookups runs on one
 // XCD (each XCD has its own L2), see lookup_index().
-// (LM_LK_OUTLIER_BIT, local_genome, genome_kept and lookup_range: lm_lookup_dev.h, shared with lm_screen.hip)
+// (LM_LK_OUTLIER_BIT, local_genome, genome_kept, lookup_range and the start rule screen_shadowed: lm_lookup_dev.h, shared
+// with lm_screen.hip)
 __device__ __forceinline__ uint32_t lookup_sort_key(const DevIndexView &ix, uint32_t md, uint64_t x) {
     const int p = ix.mask_prefix;
     const uint64_t mp = ix.masks[md >> 1] >> ((ix.K - p) << 1);
@@ -297,7 +298,8 @@ __global__ __launch_bounds__(256) void k_lookup_count(DevIndexView ix, const uin
                                                       int64_t nlk, int min_prefix, uint32_t *__restrict__ counts,
                                                       int64_t *__restrict__ starts, int32_t *__restrict__ nscan,
                                                       unsigned long long *__restrict__ stat_values,
-                                                      uint64_t *__restrict__ lkey, uint64_t *__restrict__ lrec) {
+                                                      uint64_t *__restrict__ lkey, uint64_t *__restrict__ lrec,
+                                                      ScreenShadowTab tab) {
     const int64_t j = lookup_index(nlk);
     if (j < 0) return;
     const uint32_t sk = skeys[j];
@@ -310,9 +312,11 @@ __global__ __launch_bounds__(256) void k_lookup_count(DevIndexView ix, const uin
     lookup_range(key, ix.K, min_prefix, &left, &right);
     int64_t st;
     int32_t nv = 0, nkept = 0;
+    uint32_t md;
     if (!(sk >> LM_LK_OUTLIER_BIT)) {
         const int pb = ix.part_bases << 1;
-        const uint32_t md = sk >> pb, part = sk & ((1u << pb) - 1);
+        const uint32_t part = sk & ((1u << pb) - 1);
+        md = sk >> pb;
         const uint32_t *row = ix.part_tab + (int64_t)md * ix.P1 + part;
         const int64_t base = ix.md_off[md];
         const uint64_t km = (1ull << ix.key_bits) - 1;
@@ -326,7 +330,7 @@ __global__ __launch_bounds__(256) void k_lookup_count(DevIndexView ix, const uin
             nkept = nv;
         }
     } else {
-        const uint32_t md = sk & 0x7fffffffu;
+        md = sk & 0x7fffffffu;
         int64_t lo = ix.out_off[md], hi = ix.out_off[md + 1];
         const int64_t e = hi;
         while (lo < hi) {
@@ -344,6 +348,13 @@ __global__ __launch_bounds__(256) void k_lookup_count(DevIndexView ix, const uin
             nkept = 0;
             for (int32_t x = 0; x < nv; x++) nkept += genome_kept(ix, local_genome(ix, ix.out_vals[st + x] >> 30));
         }
+    }
+    if (nv) {
+        // The reference starts its search from the anchor index of the mask's whole list, where a later run of k-mers with
+        // the range's anchor bases hides this one (screen_shadowed).  Only a list that holds k-mers of other prefixes than
+        // its mask's - outliers, of either direction - can have a second run.
+        const int64_t *oo = (tab.bits ? tab.off : ix.out_off) + (md & ~1u);
+        if (oo[2] > oo[0] && screen_shadowed(ix, tab, md >> 1, key, right)) nv = nkept = 0;
     }
     const int64_t l0 = klo[qm], l1 = khi[qm];
     counts[j] = (uint32_t)nkept * (uint32_t)(l1 - l0);
@@ -2584,9 +2595,10 @@ static int lookup_grid(int64_t total) { // one thread per lookup, workgroup coun
 }
 void launch_lookup_count(hipStream_t st, DevIndexView ix, const uint64_t *kmers, const int64_t *klo, const int64_t *khi,
                          const uint32_t *skeys, const uint32_t *sslots, int64_t nlk, int min_prefix, uint32_t *counts,
-                         int64_t *starts, int32_t *nscan, unsigned long long *stat_values, uint64_t *lkey, uint64_t *lrec) {
+                         int64_t *starts, int32_t *nscan, unsigned long long *stat_values, uint64_t *lkey, uint64_t *lrec,
+                         ScreenShadowTab tab) {
     hipLaunchKernelGGL(k_lookup_count, dim3(lookup_grid(nlk)), dim3(256), 0, st, ix, kmers, klo, khi, skeys, sslots, nlk,
-                       min_prefix, counts, starts, nscan, stat_values, lkey, lrec);
+                       min_prefix, counts, starts, nscan, stat_values, lkey, lrec, tab);
 }
 void launch_lookup_emit_flat(hipStream_t st, DevIndexView ix, const uint32_t *vals_all, const uint32_t *skeys, const uint32_t *sslots,
                              int64_t nlk, const uint32_t *counts, const int64_t *offs, const int64_t *starts, const uint64_t *lkey,

@@ -700,7 +700,9 @@ static void stage_lookup(Work &w, lm_stage_stats &stats) {
     {
         Prof p(ix, "k_lookup_count");
         launch_lookup_count(S(ix), ix->view, w.kmers.p, w.klo.p, w.khi.p, w.lk_list2.p, w.lk_perm2.p, nlk, ix->opt.min_prefix,
-                            w.lk_counts.p, w.lk_starts.p, w.lk_nscan.p, w.stat.p, w.lk_key.p, w.lk_rec.p);
+                            w.lk_counts.p, w.lk_starts.p, w.lk_nscan.p, w.stat.p, w.lk_key.p, w.lk_rec.p,
+                            ix->sc_set ? ScreenShadowTab{ix->d_sc_bits.p, ix->d_sc_sum.p, ix->d_sc_kmers.p, ix->d_sc_off.p, ix->sc_W}
+                                       : ScreenShadowTab{nullptr, nullptr, nullptr, nullptr, 0}); // (another shard's lists: lm_index_screen_add_structure)
     }
     int64_t T;
     {

@@ -97,89 +97,8 @@ __global__ __launch_bounds__(256) void k_screen_prep(DevIndexView ix, const uint
     }
 }
 
-// The reference finds the start of a search through the anchor index of a mask's list (kv-reader.go:762-1021 builds it while
-// it reads, kv-searcher2.go:326-549 uses it): index[anchor] = where a run of consecutive k-mers with these a anchor bases
-// begins in the list - ALL seeds of the mask, normal and reversed, sorted by k-mer - and a LATER run with the same anchor bases
-// overwrites an earlier one.  In a list whose k-mers all start with the mask's prefix every anchor has one run.  A list that
-// also holds k-mers of other prefixes (the captures of genomes without the mask's prefix: tiny genomes) can hold a second
-// run, and then a search for a k-mer of the earlier run starts behind its range and returns nothing.  So: walking the list
-// upwards from the searched range, k-mers with the range's anchor continue its run until one with another anchor ends it; one
-// more k-mer with that anchor afterwards and the lookup is empty.  Here the list is four sorted pieces - the packed partitions
-// and the flat outliers of both directions; the partitions share the mask's prefix, so they are one stretch of the walk and
-// the partition table says whether it holds anchors below, at and above the range's.
-// A shard holds the seeds of its own records only, so its lists are not the index's lists.  ScreenShadowTab is the part of
-// ALL shards' lists this walk reads - per list the occupied partitions as a bitmap (W words, `sum`: which words are not 0)
-// and the outlier k-mers, without values - put together by lm_index_screen_add_structure from what
-// lm_index_screen_structure exports of every shard; bits == null: the handle's own lists are the index's.
-struct ScreenShadowTab {
-    const uint64_t *bits, *sum, *kmers;
-    const int64_t *off;
-    int W;
-};
-__device__ bool screen_shadowed(const DevIndexView &ix, const ScreenShadowTab &T, uint32_t m, uint64_t x, uint64_t right) {
-    const uint64_t *out_kmers = T.bits ? T.kmers : ix.out_kmers;
-    const int64_t *out_off = T.bits ? T.off : ix.out_off;
-    const int sh = (ix.K - ix.mask_prefix) << 1;
-    const uint64_t am = (uint64_t)(ix.P1 - 2);
-    const uint64_t A = (x >> ix.key_bits) & am, tx = x >> sh, mp = ix.masks[m] >> sh;
-    bool m_less = false, m_at = false, m_more = false;
-    int64_t at[2], end[2];
-    for (int dir = 0; dir < 2; dir++) {
-        if (T.bits) {
-            const int64_t md = 2 * (int64_t)m + dir;
-            const int w = (int)(A >> 6), b = (int)(A & 63);
-            const uint64_t word = T.bits[md * T.W + w], sum = T.sum[md];
-            m_less |= (sum & ((1ull << w) - 1)) != 0 || (word & ((1ull << b) - 1)) != 0;
-            m_at |= ((word >> b) & 1ull) != 0;
-            m_more |= (w < 63 && (sum >> (w + 1)) != 0) || (b < 63 && (word >> (b + 1)) != 0);
-        } else {
-            const uint32_t *row = ix.part_tab + (int64_t)(2 * m + dir) * ix.P1;
-            m_less |= row[A] > row[0];
-            m_at |= row[A + 1] > row[A];
-            m_more |= row[ix.P1 - 1] > row[A + 1];
-        }
-        int64_t lo = out_off[2 * m + dir], hi = out_off[2 * m + dir + 1];
-        end[dir] = hi;
-        while (lo < hi) { // the first outlier above the range
-            const int64_t mid = (lo + hi) >> 1;
-            if (out_kmers[mid] <= right) lo = mid + 1;
-            else hi = mid;
-        }
-        at[dir] = lo;
-    }
-    bool ended = false, main_done = tx > mp;
-    if (tx == mp) { // the range lies in the partitions: what follows it there, then the outliers above
-        ended = m_more;
-        main_done = true;
-    }
-    for (;;) {
-        const bool h0 = at[0] < end[0], h1 = at[1] < end[1];
-        uint64_t y = 0;
-        int from = -1;
-        if (h0) {
-            y = out_kmers[at[0]];
-            from = 0;
-        }
-        if (h1 && (!h0 || out_kmers[at[1]] < y)) {
-            y = out_kmers[at[1]];
-            from = 1;
-        }
-        if (!main_done && (from < 0 || (y >> sh) > mp)) { // the partitions come first
-            if (m_less) ended = true;
-            if (m_at && ended) return true;
-            if (m_more) ended = true;
-            main_done = true;
-            continue;
-        }
-        if (from < 0) return false;
-        if (((y >> ix.key_bits) & am) == A) {
-            if (ended) return true;
-        } else {
-            ended = true;
-        }
-        at[from]++;
-    }
-}
+// (screen_shadowed, ScreenShadowTab - the reference's anchor-index start rule - live in lm_lookup_dev.h: the read search applies
+// the same rule)
 
 // the occupied partitions of every list: bits[md * W + w] bit b = partition w * 64 + b of list md holds a seed
 __global__ void k_screen_occupancy(DevIndexView ix, int W, uint64_t *__restrict__ bits) {
@@ -732,7 +651,7 @@ extern "C" lm_status lm_index_screen_genomes(lm_index *ix, const lm_genome_query
 }
 
 
-// ---- the list structure of a shard (ScreenShadowTab above).  Blob: magic, K, M, mask prefix, anchor bases, W, outlier count;
+// ---- the list structure of a shard (ScreenShadowTab, lm_kernels.h).  Blob: magic, K, M, mask prefix, anchor bases, W, outlier count;
 // bits [2M * W]; off [2M + 1]; k-mers.
 namespace lm {
 static const uint64_t SC_BLOB_MAGIC = 0x314254534d4c; // "LMSTB1"
