@@ -409,6 +409,61 @@ int lm_format_screen_row(const lm_screen_row *row, const uint8_t *prefixes, cons
                          int extra, char *buf, size_t buflen);
 /* the header line of -S (search-genome.go:482-486), no newline */
 const char *lm_screen_header(int extra);
+/* ---------------------------------------------------------------------------------------------------------
+ * Similar genome pairs: which records of this index are near-duplicates of each other?  What `lexicmap genome pair`
+ * computes with -s 0 (lexicmap/cmd/pair.go), on the device from the packed image alone (lexicmap_amd/csrc/lm_pairs.hip; the
+ * rule, the passes and their memory: DESIGN.md section 11).  The genome bytes are not read, so it works wherever they live,
+ * on built, opened, extended, joined and subset handles.
+ *   Masks (-m, :162-184): masks == 0 takes every mask; otherwise the FIRST mask (index order) of every distinct q-base prefix,
+ *     q = log4(masks).  total_masks = the number of masks taken (the distinct prefixes present, not necessarily `masks`).
+ *   Seeds: the forward seeds of a taken mask (both strands).  Two seeds of one mask match when their k-mers share at least
+ *     min_prefix (-p) leading bases; per mask and unordered pair of DIFFERENT records the largest common prefix over all
+ *     matching seed pairs counts (:903-931, :943-962).  n_masks = masks in which the pair matched, sum_prefix = the sum of
+ *     those per-mask maxima (:286-291).
+ *   Rows (:704, :995-1004): pairs with n_masks >= required = (int)(min_mask_fraction * total_masks) (-f), ordered by n_masks
+ *     descending, sum_prefix descending, (key1, key2) ascending; key1 < key2.  A split genome's records are separate
+ *     "genomes" here, as in the reference.
+ *   -s/--prob-threshold is always 0: the reference's probabilistic pruning depends on the order in which its workers deliver
+ *     masks and is not reproduced.  A pair is dropped early only when n_masks so far + masks not yet processed < required,
+ *     which changes no row.
+ *   min_prefix must lie in [mask_prefix + anchor_prefix, k]: a group of matching seeds then lies inside one partition of the
+ *     packed list or inside the outlier list.  The shorter prefixes the reference accepts are not supported.
+ *   keys / nkeys as in lm_index_seed_positions: NULL = every record of the handle; otherwise only seeds of the given records
+ *     take part (pairs among a subset of a big index); keys != NULL with nkeys == 0: no rows.  The genome whitelist of
+ *     lm_index_set_genome_filter is NOT consulted.
+ * LM_ERR_OPTION, text in lm_last_error(idx), handle still usable: min_prefix out of range; masks neither 0 nor a power of 4
+ * >= 64, or above the index's mask count; min_mask_fraction negative or NaN.  LM_ERR_ARG: a key that is no record, a key given
+ * twice, keys == NULL with nkeys > 0, a sharded handle (a shard cannot see the pairs across shards).  LM_ERR_NOMEM (the text
+ * says what had to fit): the 36 B per forward seed of the taken masks and records, the 25 B per candidate seed pair of ONE
+ * mask (the tuples pass through the device in pieces of whole masks), or the 32 B per row of the pair table, which stays on
+ * the device until the end.  LM_PAIR_PIECE_TUPLES=<n> (tests and measurement only, read at call time) caps a piece at n tuples
+ * (or one mask's, when that is more); no result depends on it.  opt == NULL: the defaults. */
+typedef struct lm_pair_opt {       /* lm_pair_opt_default(): the flag defaults of pair.go */
+    int32_t min_prefix;            /* 21 */
+    int32_t masks;                 /* 1024 */
+    double min_mask_fraction;      /* 0.25 */
+} lm_pair_opt;
+typedef struct lm_pair_row {
+    uint64_t key1, key2;           /* record keys, key1 < key2 */
+    const char *genome1, *genome2; /* borrowed from the index, valid until lm_index_close */
+    uint32_t n_masks, sum_prefix;
+} lm_pair_row;
+typedef struct lm_pair_stats {     /* measured work of the call */
+    int64_t total_masks, required, entries, tuples, pieces, pairs_seen, rows; /* entries: seeds that took part; pairs_seen: distinct pairs that entered the table */
+    double ms_entries, ms_emit, ms_reduce, ms_total;
+} lm_pair_stats;
+typedef struct lm_pairs lm_pairs;
+void lm_pair_opt_default(lm_pair_opt *o);
+lm_status lm_index_genome_pairs(lm_index *idx, const uint64_t *keys, size_t nkeys, const lm_pair_opt *opt, lm_pairs **out);
+/* returns the row count; rows may be NULL; valid until lm_pairs_free */
+size_t lm_pairs_rows(const lm_pairs *p, const lm_pair_row **rows);
+void lm_pairs_get_stats(const lm_pairs *p, lm_pair_stats *s);
+void lm_pairs_free(lm_pairs *p);
+/* One line of `lexicmap genome pair` (pair.go:730; no newline): genome1, genome2, minPrefix, fracMasks = n_masks /
+ * total_masks, nMasks, sumPrefix, avgPrefix as "%s\t%s\t%d\t%.4f\t%d\t%d\t%.2f".  Returns the length that was / would be written. */
+int lm_format_pair_row(const lm_pair_row *r, int min_prefix, int total_masks, char *buf, size_t cap);
+/* its header line (pair.go:721), no newline */
+const char *lm_pair_header(void);
 /* text of the last error on this handle, or of the last failed lm_index_open when idx == NULL */
 const char *lm_last_error(const lm_index *idx);
 

@@ -156,6 +156,20 @@ class ScreenStats(C.Structure):
                [(n, C.c_double) for n in ("ms_capture", "ms_lookup", "ms_reduce", "ms_total")]
 
 
+class PairOpt(C.Structure):
+    _fields_ = [("min_prefix", C.c_int32), ("masks", C.c_int32), ("min_mask_fraction", C.c_double)]
+
+
+class PairRow(C.Structure):
+    _fields_ = [("key1", C.c_uint64), ("key2", C.c_uint64), ("genome1", C.c_char_p), ("genome2", C.c_char_p),
+                ("n_masks", C.c_uint32), ("sum_prefix", C.c_uint32)]
+
+
+class PairStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("total_masks", "required", "entries", "tuples", "pieces", "pairs_seen", "rows")] + \
+               [(n, C.c_double) for n in ("ms_entries", "ms_emit", "ms_reduce", "ms_total")]
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char_p), ("launches", C.c_int64), ("total_ms", C.c_double), ("bytes", C.c_int64)]
 
@@ -272,6 +286,18 @@ def lib():
                                        C.c_char_p, C.c_size_t]
     L.lm_screen_header.argtypes = [C.c_int]
     L.lm_screen_header.restype = C.c_char_p
+    L.lm_pair_opt_default.argtypes = [C.POINTER(PairOpt)]
+    L.lm_pair_opt_default.restype = None
+    L.lm_index_genome_pairs.argtypes = [vp, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(PairOpt), C.POINTER(vp)]
+    L.lm_pairs_rows.argtypes = [vp, C.POINTER(C.POINTER(PairRow))]
+    L.lm_pairs_rows.restype = C.c_size_t
+    L.lm_pairs_get_stats.argtypes = [vp, C.POINTER(PairStats)]
+    L.lm_pairs_get_stats.restype = None
+    L.lm_pairs_free.argtypes = [vp]
+    L.lm_pairs_free.restype = None
+    L.lm_format_pair_row.argtypes = [C.POINTER(PairRow), C.c_int, C.c_int, C.c_char_p, C.c_size_t]
+    L.lm_pair_header.argtypes = []
+    L.lm_pair_header.restype = C.c_char_p
     L.lm_index_screen_structure.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.lm_index_screen_add_structure.argtypes = [vp, C.c_char_p, C.c_size_t]
     L.lm_index_fetch.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, C.c_char_p]
@@ -581,6 +607,47 @@ class Index:
             return out, {f[0]: getattr(stt, f[0]) for f in ScreenStats._fields_}
         finally:
             L.lm_screen_free(sc)
+
+    def pairs(self, keys=None, min_prefix=21, masks=1024, min_mask_fraction=0.25, want_stats=False, arrays=False):
+        """lm_index_genome_pairs: the similar record pairs of this index - what `lexicmap genome pair -s 0` prints -
+        computed on the GPU from the resident seed image.  keys: record keys (batch << 17 | index) to look among, None:
+        every record; the whitelist of set_genome_filter is not consulted.  masks: 0 = all masks, else a power of 4 >= 64
+        (the first mask of every prefix of log4(masks) bases).  -> the rows in output order (n_masks descending, sum_prefix
+        descending, (key1, key2) ascending) as a list of dicts key1, key2, genome1, genome2, n_masks, sum_prefix; with
+        arrays=True as ONE numpy structured array (key1, key2, n_masks, sum_prefix) without the names, for results of
+        millions of rows.  want_stats: (rows, stats dict); stats["total_masks"] is what format_pair_rows takes.
+        ValueError for what the library refuses as an argument or option (an unknown or repeated key, a sharded handle,
+        min_prefix outside [mask_prefix + anchor_prefix, k], masks, a negative min_mask_fraction)."""
+        import numpy as np
+        L = lib()
+        arr, n = self._record_keys(keys)
+        opt = PairOpt(min_prefix, masks, min_mask_fraction)
+        pr = C.c_void_p()
+        st = L.lm_index_genome_pairs(self.h, arr, n, C.byref(opt), C.byref(pr))
+        if st in (3, 7):
+            raise ValueError(L.lm_last_error(self.h).decode())
+        if st != 0:
+            self._err(st)
+        try:
+            rows_p = C.POINTER(PairRow)()
+            nr = L.lm_pairs_rows(pr, C.byref(rows_p))
+            if arrays:
+                raw = np.dtype([("key1", np.uint64), ("key2", np.uint64), ("genome1", np.uintp), ("genome2", np.uintp),
+                                ("n_masks", np.uint32), ("sum_prefix", np.uint32)])   # PairRow, the pointers as numbers
+                assert raw.itemsize == C.sizeof(PairRow)
+                full = np.frombuffer(C.string_at(rows_p, nr * raw.itemsize), dtype=raw) if nr else np.zeros(0, raw)
+                out = np.zeros(nr, dtype=[("key1", np.uint64), ("key2", np.uint64), ("n_masks", np.uint32), ("sum_prefix", np.uint32)])
+                for f in out.dtype.names:
+                    out[f] = full[f]
+            else:
+                out = [{f[0]: getattr(rows_p[i], f[0]) for f in PairRow._fields_} for i in range(nr)]
+            if not want_stats:
+                return out
+            stt = PairStats()
+            L.lm_pairs_get_stats(pr, C.byref(stt))
+            return out, {f[0]: getattr(stt, f[0]) for f in PairStats._fields_}
+        finally:
+            L.lm_pairs_free(pr)
 
     def screen_structure(self):
         """lm_index_screen_structure: what screening reads of this handle's lists beyond its own seeds (occupied partitions,
@@ -1078,6 +1145,23 @@ def format_screen_rows(rows, query_ids, min_prefix, masks, extra=False, header=F
                 buf = C.create_string_buffer(n + 1)
                 L.lm_format_screen_row(C.byref(r), pref, qb, min_prefix, masks, 1 if extra else 0, buf, len(buf))
             out.append(buf.value.decode())
+    return out
+
+
+def format_pair_rows(rows, min_prefix, total_masks, header=False):
+    """the lines `lexicmap genome pair` prints for the rows Index.pairs returned (the list of dicts), each formatted by
+    lm_format_pair_row; header: lm_pair_header first.  total_masks: stats["total_masks"] of the call."""
+    L = lib()
+    out = [L.lm_pair_header().decode()] if header else []
+    buf = C.create_string_buffer(1 << 12)
+    for d in rows:
+        g1, g2 = (x if isinstance(x, bytes) or x is None else str(x).encode() for x in (d["genome1"], d["genome2"]))
+        r = PairRow(d["key1"], d["key2"], g1, g2, d["n_masks"], d["sum_prefix"])
+        n = L.lm_format_pair_row(C.byref(r), min_prefix, total_masks, buf, len(buf))
+        if n >= len(buf):
+            buf = C.create_string_buffer(n + 1)
+            L.lm_format_pair_row(C.byref(r), min_prefix, total_masks, buf, len(buf))
+        out.append(buf.value.decode())
     return out
 
 
