@@ -539,6 +539,81 @@ lm_status lm_format_rows(const lm_hsp *rows, size_t n, const char *const *query_
 /* the header line of the TSV (search.go:426-430), no newline; more_columns as in lm_format_row */
 const char *lm_tsv_header(int more_columns);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Subject subsequences and flanks: the bases around the hits of a search, or of any region of a record, from the resident
+ * 2-bit genomes in one batched device pass.  What `lexicmap utils subseq` and `lexicmap utils genome-seqs` print
+ * (lexicmap/cmd/subseq.go, genome-seqs.go; genome/genome.go SubSeq, SubSeq2), with the rule, the passes and their memory in
+ * DESIGN.md section 11 (lexicmap_amd/csrc/lm_subseq_plan.h, lm_subseq.hip).
+ *   A region names a record by key (batch << 17 | index), or with key == LM_REGION_BY_NAME by genome_id: the genome's records
+ *     are tried in chunk order and the first one that holds the contig id answers (subseq.go:403-423).
+ *   The contig: seq_id (non-empty) by id; else seq_idx >= 0 by number (what lm_hsp carries; with a genome id: of the genome's
+ *     first record); else (seq_idx < 0) begin / end are concatenated coordinates of the record (-c/--concatenated-positions).
+ *   begin <= end are 1-based and inclusive; rc != 0 is the '-' strand: the reverse complement of the same bases, begin / end
+ *     stay forward coordinates.  upstream / downstream (-U / -D) extend the region and swap on the '-' strand; the start is
+ *     clamped to 1, the end to the contig (to the record in concatenated coordinates): a flank never runs into the spacer
+ *     between two contigs.  A region that begins behind its contig's end is answered with no bases.  N is stored as A.
+ *   Status per region: LM_SUBSEQ_NO_GENOME (no such key / genome id), LM_SUBSEQ_NO_SEQ (the contig is in none of the genome's
+ *     records, a seq_idx beyond the record, or a contig id that occurs twice in one record - name such a contig by seq_idx),
+ *     LM_SUBSEQ_OUT_OF_RANGE (concatenated coordinates that begin behind the record's end), LM_SUBSEQ_NOT_LOCAL (a sharded
+ *     handle answers for its own records; regions by genome id see the shard's own genomes only).
+ *   ignore_errors == 0 (the tool without -e): the first region with a status other than OK makes the call return LM_ERR_ARG,
+ *     lm_last_error names the region and what failed, nothing is returned.  ignore_errors != 0 (-e): such regions carry their
+ *     status and no bases, the others are answered.  begin < 1, end < begin and negative flanks are LM_ERR_ARG in either mode,
+ *     and so is a region of 2^31 bases or more or one whose first base lies behind base 2^32 of its record.
+ *   The result: one lm_subseq_info per region, in region order, and ONE blob of ASCII bases (pinned host memory): region i's
+ *     bases are blob[off, off + len); off is a multiple of 16, the bytes between two regions are zero.  begin / end are the
+ *     extracted range as the tool prints it.  The blob passes through the device in pieces of LM_SUBSEQ_PIECE_BYTES (read at
+ *     call time; tests and measurement), by default 256 MB or what the scratch arena can give; no result depends on it.
+ * The genome whitelist of lm_index_set_genome_filter is not consulted.  opt == NULL: no flanks, errors are errors. */
+enum { LM_SUBSEQ_OK = 0, LM_SUBSEQ_NO_GENOME = 1, LM_SUBSEQ_NO_SEQ = 2, LM_SUBSEQ_OUT_OF_RANGE = 3, LM_SUBSEQ_NOT_LOCAL = 4 };
+#define LM_REGION_BY_NAME UINT64_MAX
+typedef struct lm_region {
+    uint64_t key;           /* record key, or LM_REGION_BY_NAME */
+    const char *genome_id;  /* used with LM_REGION_BY_NAME */
+    const char *seq_id;     /* NULL or "": see seq_idx */
+    int32_t seq_idx;        /* >= 0: contig by number; < 0 with no seq_id: concatenated coordinates */
+    int32_t rc;
+    int64_t begin, end;     /* 1-based, inclusive */
+} lm_region;
+typedef struct lm_subseq_opt {
+    int32_t upstream, downstream, ignore_errors, pad;
+} lm_subseq_opt;
+typedef struct lm_subseq_info {
+    uint64_t key;           /* the record that answered (0 when none did) */
+    int32_t seq_idx;        /* its contig, -1 in concatenated coordinates */
+    int32_t status;         /* LM_SUBSEQ_* */
+    int32_t rc, pad;
+    int64_t begin, end;     /* the extracted range: start after the flank and the clamp, reported end */
+    int64_t off, len;       /* into the base blob */
+    const char *genome_id, *seq_id; /* borrowed from the index, valid until lm_index_close; seq_id NULL in concatenated coordinates */
+} lm_subseq_info;
+typedef struct lm_subseq_stats {   /* measured work of the call */
+    int64_t regions, answered, bases, blob_bytes, pieces;
+    double ms_plan, ms_alloc, ms_device, ms_total; /* ms_alloc: pinning the blob; ms_device: the extraction kernels alone (events around each launch) */
+} lm_subseq_stats;
+typedef struct lm_subseqs lm_subseqs;
+void lm_subseq_opt_default(lm_subseq_opt *o);
+lm_status lm_index_subseqs(lm_index *idx, const lm_region *regions, size_t n, const lm_subseq_opt *opt, lm_subseqs **out);
+/* the subject region of every row: key = batch_genome, contig seq_idx, tbegin + 1 .. tend + 1, strand rc (what
+ * `lexicmap utils subseq -f` reads from the TSV's sgenome, sseqid, sstart, send, sstr); rows of a gathered or merged result too */
+lm_status lm_index_subseq_rows(lm_index *idx, const lm_hsp *rows, size_t n, const lm_subseq_opt *opt, lm_subseqs **out);
+/* `lexicmap utils genome-seqs` (genome-seqs.go:115-137): every contig of every record of the genome, whole, forward, in record
+ * and contig order.  An unknown genome id is LM_ERR_ARG. */
+lm_status lm_index_genome_seqs(lm_index *idx, const char *genome_id, lm_subseqs **out);
+/* returns the region count; info / bases may be NULL; valid until lm_subseqs_free */
+size_t lm_subseqs_get(const lm_subseqs *s, const lm_subseq_info **info, const char **bases);
+void lm_subseqs_get_stats(const lm_subseqs *s, lm_subseq_stats *stats);
+void lm_subseqs_free(lm_subseqs *s);
+/* The FASTA text of a result, formatted by the host threads into ONE buffer (*text, *len bytes, released with lm_free).  Per
+ * region with status OK: ">%s:%d-%d:%s" with the contig id (the genome id in concatenated coordinates), begin, end and strand
+ * (subseq.go:632-636); the bases in lines of line_width (line_width <= 0: one line; util.go:311-347), an empty sequence as an
+ * empty line; a newline.  Regions with another status print nothing (subseq.go:233-243).  With rows (as many as regions, the
+ * rows lm_index_subseq_rows was given; query_ids / query_lens / nq as in lm_format_rows) the header is the long one of
+ * subseq.go:204-205, 447-450, its fields the row's TSV columns as lm_format_row prints them.  A result of
+ * lm_index_genome_seqs prints just ">seqid". */
+lm_status lm_format_subseqs(const lm_subseqs *s, const lm_hsp *rows, const char *const *query_ids, const uint32_t *query_lens, size_t nq,
+                            int line_width, char **text, size_t *len);
+
 typedef struct lm_stage lm_stage; /* host arrays of a stage-level call, released with lm_stage_free */
 
 /* ---------------------------------------------------------------------------------------------------------

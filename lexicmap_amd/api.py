@@ -170,6 +170,30 @@ class PairStats(C.Structure):
                [(n, C.c_double) for n in ("ms_entries", "ms_emit", "ms_reduce", "ms_total")]
 
 
+REGION_BY_NAME = (1 << 64) - 1   # LM_REGION_BY_NAME
+SUBSEQ_OK, SUBSEQ_NO_GENOME, SUBSEQ_NO_SEQ, SUBSEQ_OUT_OF_RANGE, SUBSEQ_NOT_LOCAL = range(5)
+
+
+class Region(C.Structure):
+    _fields_ = [("key", C.c_uint64), ("genome_id", C.c_char_p), ("seq_id", C.c_char_p), ("seq_idx", C.c_int32),
+                ("rc", C.c_int32), ("begin", C.c_int64), ("end", C.c_int64)]
+
+
+class SubseqOpt(C.Structure):
+    _fields_ = [("upstream", C.c_int32), ("downstream", C.c_int32), ("ignore_errors", C.c_int32), ("pad", C.c_int32)]
+
+
+class SubseqInfo(C.Structure):
+    _fields_ = [("key", C.c_uint64), ("seq_idx", C.c_int32), ("status", C.c_int32), ("rc", C.c_int32), ("pad", C.c_int32),
+                ("begin", C.c_int64), ("end", C.c_int64), ("off", C.c_int64), ("len", C.c_int64),
+                ("genome_id", C.c_char_p), ("seq_id", C.c_char_p)]
+
+
+class SubseqStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("regions", "answered", "bases", "blob_bytes", "pieces")] + \
+               [(n, C.c_double) for n in ("ms_plan", "ms_alloc", "ms_device", "ms_total")]
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char_p), ("launches", C.c_int64), ("total_ms", C.c_double), ("bytes", C.c_int64)]
 
@@ -298,6 +322,19 @@ def lib():
     L.lm_format_pair_row.argtypes = [C.POINTER(PairRow), C.c_int, C.c_int, C.c_char_p, C.c_size_t]
     L.lm_pair_header.argtypes = []
     L.lm_pair_header.restype = C.c_char_p
+    L.lm_subseq_opt_default.argtypes = [C.POINTER(SubseqOpt)]
+    L.lm_subseq_opt_default.restype = None
+    L.lm_index_subseqs.argtypes = [vp, C.POINTER(Region), C.c_size_t, C.POINTER(SubseqOpt), C.POINTER(vp)]
+    L.lm_index_subseq_rows.argtypes = [vp, C.POINTER(Hsp), C.c_size_t, C.POINTER(SubseqOpt), C.POINTER(vp)]
+    L.lm_index_genome_seqs.argtypes = [vp, C.c_char_p, C.POINTER(vp)]
+    L.lm_subseqs_get.argtypes = [vp, C.POINTER(C.POINTER(SubseqInfo)), C.POINTER(vp)]
+    L.lm_subseqs_get.restype = C.c_size_t
+    L.lm_subseqs_get_stats.argtypes = [vp, C.POINTER(SubseqStats)]
+    L.lm_subseqs_get_stats.restype = None
+    L.lm_subseqs_free.argtypes = [vp]
+    L.lm_subseqs_free.restype = None
+    L.lm_format_subseqs.argtypes = [vp, C.POINTER(Hsp), C.POINTER(C.c_char_p), C.POINTER(C.c_uint32), C.c_size_t, C.c_int,
+                                    C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.lm_index_screen_structure.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.lm_index_screen_add_structure.argtypes = [vp, C.c_char_p, C.c_size_t]
     L.lm_index_fetch.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, C.c_char_p]
@@ -648,6 +685,50 @@ class Index:
             return out, {f[0]: getattr(stt, f[0]) for f in PairStats._fields_}
         finally:
             L.lm_pairs_free(pr)
+
+    def _subseq_result(self, st, sp):
+        if st == 7:
+            raise ValueError(lib().lm_last_error(self.h).decode())
+        if st != 0:
+            self._err(st)
+        return Subseqs(sp)
+
+    def subseq(self, regions, upstream=0, downstream=0, ignore_errors=False):
+        """lm_index_subseqs: the bases of regions of this index's records with flanks - what `lexicmap utils subseq` prints -
+        extracted on the GPU from the resident 2-bit genomes.  regions: dicts with `key` (record key batch << 17 | index) or
+        `genome_id`; `seq_id` or `seq_idx` (neither: concatenated coordinates); `begin`, `end` (1-based, inclusive); `rc`.
+        -> Subseqs.  ValueError for what the library refuses as an argument: begin < 1, end < begin, a negative flank, and -
+        unless ignore_errors - the first region that cannot be answered."""
+        L = lib()
+        arr = (Region * max(len(regions), 1))()
+        keep = []
+        for i, d in enumerate(regions):
+            gid, sid = ((x if isinstance(x, bytes) or x is None else str(x).encode()) for x in (d.get("genome_id"), d.get("seq_id")))
+            keep += [gid, sid]
+            key = d.get("key")
+            arr[i] = Region(REGION_BY_NAME if key is None else int(key), gid, sid, int(d.get("seq_idx", -1)),
+                            1 if d.get("rc") else 0, int(d["begin"]), int(d["end"]))
+        opt = SubseqOpt(upstream, downstream, 1 if ignore_errors else 0, 0)
+        sp = C.c_void_p()
+        return self._subseq_result(L.lm_index_subseqs(self.h, arr, len(regions), C.byref(opt), C.byref(sp)), sp)
+
+    def subseq_rows(self, rows, upstream=0, downstream=0, ignore_errors=False):
+        """lm_index_subseq_rows: the subject region of every search row (a numpy row array of merge.ROW_DTYPE, or the list
+        of dicts Index.search returns) with flanks -> Subseqs, one entry per row"""
+        import numpy as np
+        from .merge import ROW_DTYPE, pack_rows
+        arr = pack_rows(rows) if isinstance(rows, list) else np.ascontiguousarray(rows, dtype=ROW_DTYPE)
+        opt = SubseqOpt(upstream, downstream, 1 if ignore_errors else 0, 0)
+        sp = C.c_void_p()
+        st = lib().lm_index_subseq_rows(self.h, arr.ctypes.data_as(C.POINTER(Hsp)), len(arr), C.byref(opt), C.byref(sp))
+        return self._subseq_result(st, sp)
+
+    def genome_seqs(self, genome_id):
+        """lm_index_genome_seqs: every contig of every record of a genome, whole and forward, in record and contig order
+        (`lexicmap utils genome-seqs`) -> Subseqs; ValueError for an unknown genome id"""
+        sp = C.c_void_p()
+        gid = genome_id if isinstance(genome_id, bytes) else str(genome_id).encode()
+        return self._subseq_result(lib().lm_index_genome_seqs(self.h, gid, C.byref(sp)), sp)
 
     def screen_structure(self):
         """lm_index_screen_structure: what screening reads of this handle's lists beyond its own seeds (occupied partitions,
@@ -1162,6 +1243,64 @@ def format_pair_rows(rows, min_prefix, total_masks, header=False):
             buf = C.create_string_buffer(n + 1)
             L.lm_format_pair_row(C.byref(r), min_prefix, total_masks, buf, len(buf))
         out.append(buf.value.decode())
+    return out
+
+
+class Subseqs:
+    """lm_subseqs: the answer of Index.subseq / subseq_rows / genome_seqs.  info: one dict per region (key, seq_idx, status,
+    rc, begin, end, off, len, genome_id, seq_id); seqs: the bases of every region as bytes (b"" where status != 0); stats.
+    The library's result is released by close() or with the object."""
+
+    def __init__(self, handle):
+        L = lib()
+        self.h = handle
+        info_p, bases = C.POINTER(SubseqInfo)(), C.c_void_p()
+        self.n = L.lm_subseqs_get(self.h, C.byref(info_p), C.byref(bases))
+        self.info = [{f[0]: getattr(info_p[i], f[0]) for f in SubseqInfo._fields_ if f[0] != "pad"} for i in range(self.n)]
+        stt = SubseqStats()
+        L.lm_subseqs_get_stats(self.h, C.byref(stt))
+        self.stats = {f[0]: getattr(stt, f[0]) for f in SubseqStats._fields_}
+        self.blob = C.string_at(bases, self.stats["blob_bytes"]) if self.stats["blob_bytes"] else b""
+
+    @property
+    def seqs(self):
+        return [self.blob[d["off"]:d["off"] + d["len"]] for d in self.info]
+
+    def close(self):
+        if self.h:
+            lib().lm_subseqs_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def format_subseqs(sub, rows=None, ids=None, lens=None, line_width=60):
+    """lm_format_subseqs: the FASTA text (bytes) `lexicmap utils subseq` / `genome-seqs` print for a Subseqs.  rows (with ids /
+    lens, the id and length of every batch query): the rows Index.subseq_rows was given - the long header of
+    `utils subseq -f`.  line_width <= 0: no wrapping."""
+    import numpy as np
+    from .merge import ROW_DTYPE, pack_rows
+    L = lib()
+    rp, idarr, lnarr, nq = None, None, None, 0
+    if rows is not None:
+        # (pack_rows drops the names of a list of dicts: the formatter takes them from the result)
+        arr = pack_rows(rows) if isinstance(rows, list) else np.ascontiguousarray(rows, dtype=ROW_DTYPE)
+        if len(arr) != sub.n:
+            raise ValueError("format_subseqs: %d rows for %d regions" % (len(arr), sub.n))
+        rp = arr.ctypes.data_as(C.POINTER(Hsp))
+        idarr = (C.c_char_p * max(len(ids), 1))(*[i if isinstance(i, bytes) else str(i).encode() for i in ids])
+        lnarr = (C.c_uint32 * max(len(lens), 1))(*[int(x) for x in lens])
+        nq = len(ids)
+    text, n = C.c_void_p(), C.c_size_t(0)
+    st = L.lm_format_subseqs(sub.h, rp, idarr, lnarr, nq, line_width, C.byref(text), C.byref(n))
+    if st != 0:
+        raise RuntimeError("lm_format_subseqs failed (%d)" % st)
+    out = C.string_at(text, n.value)
+    L.lm_free(text)
     return out
 
 

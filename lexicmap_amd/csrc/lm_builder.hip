@@ -1884,7 +1884,7 @@ lm_status lm_index_fetch(lm_index *ix, int64_t local_genome, int64_t start, int6
         HIPCHK(hipSetDevice(ix->device));
         DBuf<uint8_t> d;
         d.ensure((size_t)len + 1);
-        // (a host-resident genome is read where it lives: this kernel and k_stage_genome_bits are the two that may)
+        // (a host-resident genome is read where it lives: lm_kernels.hip, k_stage_genome_bits, lists the kernels that may)
         const uint8_t *gsrc = !ix->g_hptr.empty() && ix->g_hptr[(size_t)local_genome] ? ix->g_hptr[(size_t)local_genome] : ix->d_gbits.p + G.bits_off;
         hipLaunchKernelGGL(k_fetch_bases, dim3(gridn(len)), dim3(256), 0, ix->lane[0].main.st, gsrc, start, len, d.p);
         HIPCHK(hipMemcpyAsync(out, d.p, (size_t)len, hipMemcpyDeviceToHost, ix->lane[0].main.st));

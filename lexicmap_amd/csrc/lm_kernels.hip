@@ -940,7 +940,8 @@ __global__ void k_extract_windows_at(DevIndexView ix, const Task *__restrict__ t
 // into the chunk's compact device staging buffer - one workgroup per window.  A lane loads 16 bytes, consecutive lanes
 // consecutive addresses (a wavefront asks the host link for 1 KB in one instruction, the workgroup keeps 4 KB per round in
 // flight; src and dst are multiples of 16), and stores them the same way; the LM_STAGE_TAIL bytes behind the copy are
-// zeroed.  This kernel and k_fetch_bases are the only ones that dereference host memory: the k-mer cutters of the
+// zeroed.  This kernel, k_fetch_bases and k_subseq_extract (lm_subseq.hip: aligned 32-bit words, consecutive lanes consecutive
+// addresses) are the only ones that dereference host memory: the k-mer cutters of the
 // pseudo-alignment read 8 .. 20 unaligned bytes per lane, one small transaction each over the link.
 __global__ __launch_bounds__(256) void k_stage_genome_bits(const StageCmd *__restrict__ cmds, int64_t n) {
     for (int64_t ci = blockIdx.x; ci < n; ci += gridDim.x) {
