@@ -464,6 +464,48 @@ void lm_pairs_free(lm_pairs *p);
 int lm_format_pair_row(const lm_pair_row *r, int min_prefix, int total_masks, char *buf, size_t cap);
 /* its header line (pair.go:721), no newline */
 const char *lm_pair_header(void);
+/* Pairs across the shards of a sharded index ("Pairs across shards").  Shards
+ * partition records, not masks: every shard holds every mask's seeds of its own records, and the mask selection and `required`
+ * depend on the mask set alone.  So a pair can be evaluated wholly on one rank once that rank has the forward seeds of the
+ * other record's shard.  Every rank exports its seeds once (lm_index_pair_seeds); rank r receives the blobs of the ranks
+ * s < r - the host carries them, the library moves nothing - and calls lm_index_genome_pairs_across; rank 0 merges the
+ * ranks' rows (lm_pairs_merge).  The merged rows are the unsharded index's rows, row for row.  These calls go beyond what
+ * `lexicmap genome pair` has: the reference has no shards.
+ *
+ * lm_index_pair_seeds: the forward seeds of the masks taken by opt->masks (the rule above; min_prefix and min_mask_fraction
+ * are not read) of the records keys / nkeys selects (as above), of a sharded or an unsharded handle, as (k-mer, record) in
+ * list order per mask: packed list, then outliers.  *blob / *bytes, released with lm_free.  A handle or a selection without
+ * records gives a valid blob without records.  The blob needs no alignment; its layout, all little-endian: uint64 magic;
+ * int32 k, masks of the index, opt->masks, total_masks = masks taken; uint64 fingerprint of the mask values; int64 records,
+ * entries, id_bytes; uint64 keys[records], ascending; uint16 id_len[records]; char ids[id_bytes] (the genome ids back to back,
+ * no terminators); int64 offsets[total_masks + 1] (the first entry of every taken mask); uint64 kmers[entries]; uint32
+ * record[entries] (index into keys).  12 B per seed, 10 B and its id per record.  LM_ERR_OPTION / LM_ERR_ARG as
+ * lm_index_genome_pairs for masks and keys; a genome id of more than 65535 bytes is LM_ERR_ARG.
+ *
+ * lm_index_genome_pairs_across: the rows - the rule, the order and the options of lm_index_genome_pairs, unchanged, key1 <
+ * key2 over the global record keys - of the pairs among the handle's own selected records and of the pairs between an own
+ * record and a record of any blob.  Two blob records are never a row.  The handle may be a shard or unsharded; nblobs == 0
+ * gives the pairs within the handle, which lm_index_genome_pairs refuses to give for a shard.  genome1 / genome2 of an own
+ * record are borrowed from the index as above; those of a blob record point into storage the RESULT owns and are valid until
+ * lm_pairs_free.  stats.entries counts own and blob seeds, stats.tuples the candidate seed pairs emitted: every pair of seeds
+ * of a group is emitted on exactly one rank.  LM_ERR_OPTION as lm_index_genome_pairs.  LM_ERR_ARG, the text naming the blob
+ * number and what differs, the handle as it was: a blob of another k, mask count or mask values; a blob exported with
+ * another opt->masks; a broken blob (length, offsets not monotone, a record index out of range, keys not ascending); a record
+ * key that is also an own record or occurs in two blobs; blobs == NULL with nblobs > 0; more than 2^29 records in the union.
+ * LM_ERR_NOMEM as above, the blob seeds counted in: with blob seeds the entries are sorted on the device, 32 B per seed
+ * while sorted, 49 B while the groups are scanned, 32 B afterwards.
+ *
+ * lm_pairs_from_rows: rows that reached this process some other way (a rank's rows over the wire) as a result of their
+ * own; the rows and their names are copied, stats may be NULL.  lm_pairs_merge: a host k-way merge of n results by the
+ * rule's order.  Every name is COPIED into the merged result, which does not depend on the parts or on any index afterwards.
+ * Its stats are the parts' sums (total_masks and required: the largest).  LM_ERR_ARG: a part that is NULL or not in the
+ * rule's order, a pair that occurs twice - the ranks did not follow the s < r scheme.  Neither call takes a handle: the text
+ * of a refusal is lm_last_error(NULL). */
+lm_status lm_index_pair_seeds(lm_index *idx, const uint64_t *keys, size_t nkeys, const lm_pair_opt *opt, void **blob, size_t *bytes);
+lm_status lm_index_genome_pairs_across(lm_index *idx, const uint64_t *keys, size_t nkeys, const void *const *blobs, const size_t *blob_bytes,
+                                       size_t nblobs, const lm_pair_opt *opt, lm_pairs **out);
+lm_status lm_pairs_from_rows(const lm_pair_row *rows, size_t n, const lm_pair_stats *stats, lm_pairs **out);
+lm_status lm_pairs_merge(const lm_pairs *const *parts, size_t n, lm_pairs **out);
 /* text of the last error on this handle, or of the last failed lm_index_open when idx == NULL */
 const char *lm_last_error(const lm_index *idx);
 

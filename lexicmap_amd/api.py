@@ -322,6 +322,11 @@ def lib():
     L.lm_format_pair_row.argtypes = [C.POINTER(PairRow), C.c_int, C.c_int, C.c_char_p, C.c_size_t]
     L.lm_pair_header.argtypes = []
     L.lm_pair_header.restype = C.c_char_p
+    L.lm_index_pair_seeds.argtypes = [vp, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(PairOpt), C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.lm_index_genome_pairs_across.argtypes = [vp, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t), C.c_size_t,
+                                               C.POINTER(PairOpt), C.POINTER(vp)]
+    L.lm_pairs_from_rows.argtypes = [C.POINTER(PairRow), C.c_size_t, C.POINTER(PairStats), C.POINTER(vp)]
+    L.lm_pairs_merge.argtypes = [C.POINTER(vp), C.c_size_t, C.POINTER(vp)]
     L.lm_subseq_opt_default.argtypes = [C.POINTER(SubseqOpt)]
     L.lm_subseq_opt_default.restype = None
     L.lm_index_subseqs.argtypes = [vp, C.POINTER(Region), C.c_size_t, C.POINTER(SubseqOpt), C.POINTER(vp)]
@@ -655,12 +660,50 @@ class Index:
         millions of rows.  want_stats: (rows, stats dict); stats["total_masks"] is what format_pair_rows takes.
         ValueError for what the library refuses as an argument or option (an unknown or repeated key, a sharded handle,
         min_prefix outside [mask_prefix + anchor_prefix, k], masks, a negative min_mask_fraction)."""
-        import numpy as np
-        L = lib()
         arr, n = self._record_keys(keys)
         opt = PairOpt(min_prefix, masks, min_mask_fraction)
         pr = C.c_void_p()
-        st = L.lm_index_genome_pairs(self.h, arr, n, C.byref(opt), C.byref(pr))
+        st = lib().lm_index_genome_pairs(self.h, arr, n, C.byref(opt), C.byref(pr))
+        return self._pairs_result(st, pr, want_stats, arrays)
+
+    def pair_seeds(self, keys=None, masks=1024):
+        """lm_index_pair_seeds: the forward seeds of the taken masks of this handle's (selected) records as bytes, for the
+        ranks that pair their records with these (pairs_across).  Works on shards and on unsharded handles; the blob of a
+        handle or selection without records is valid and empty.  masks must be what pairs_across is called with."""
+        L = lib()
+        arr, n = self._record_keys(keys)
+        opt = PairOpt(21, masks, 0.25)
+        p, nb = C.c_void_p(), C.c_size_t()
+        st = L.lm_index_pair_seeds(self.h, arr, n, C.byref(opt), C.byref(p), C.byref(nb))
+        if st in (3, 7):
+            raise ValueError(L.lm_last_error(self.h).decode())
+        if st != 0:
+            self._err(st)
+        try:
+            return C.string_at(p, nb.value)
+        finally:
+            L.lm_free(p)
+
+    def pairs_across(self, blobs, keys=None, min_prefix=21, masks=1024, min_mask_fraction=0.25, want_stats=False, arrays=False):
+        """lm_index_genome_pairs_across: the pairs among this handle's own (selected) records and between an own record and
+        a record of any of `blobs` (pair_seeds() of other shards, exported with the same masks) - never between two blob
+        records.  Rank r of a sharded index passes the blobs of the ranks s < r; merge_pair_rows of all ranks' rows is then
+        the unsharded index's Index.pairs, row for row.  blobs=[]: the pairs within this handle, also on a shard.  Options,
+        result and ValueError as Index.pairs; ValueError also for a blob that is broken, of other masks or another `masks`,
+        or whose records overlap the handle's or another blob's."""
+        L = lib()
+        arr, n = self._record_keys(keys)
+        opt = PairOpt(min_prefix, masks, min_mask_fraction)
+        bl = [bytes(b) for b in blobs]
+        ptrs = (C.c_char_p * max(len(bl), 1))(*bl)
+        lens = (C.c_size_t * max(len(bl), 1))(*[len(b) for b in bl])
+        pr = C.c_void_p()
+        st = L.lm_index_genome_pairs_across(self.h, arr, n, C.cast(ptrs, C.POINTER(C.c_void_p)), lens, len(bl), C.byref(opt), C.byref(pr))
+        return self._pairs_result(st, pr, want_stats, arrays)
+
+    def _pairs_result(self, st, pr, want_stats, arrays):
+        import numpy as np
+        L = lib()
         if st in (3, 7):
             raise ValueError(L.lm_last_error(self.h).decode())
         if st != 0:
@@ -1244,6 +1287,41 @@ def format_pair_rows(rows, min_prefix, total_masks, header=False):
             L.lm_format_pair_row(C.byref(r), min_prefix, total_masks, buf, len(buf))
         out.append(buf.value.decode())
     return out
+
+
+def merge_pair_rows(parts):
+    """lm_pairs_merge: the rows of several Index.pairs_across calls (lists of dicts, one list per rank) as ONE list in the
+    rule's order - what rank 0 does with the ranks' rows; each list goes through lm_pairs_from_rows, as rows that came over
+    the wire do.  ValueError when a pair occurs twice (the ranks did not follow the s < r scheme) or a list is out of order."""
+    L = lib()
+    handles, keep = [], []
+    merged = C.c_void_p()
+    try:
+        for rows in parts:
+            arr = (PairRow * max(len(rows), 1))()
+            for i, d in enumerate(rows):
+                g1, g2 = (x if isinstance(x, bytes) or x is None else str(x).encode() for x in (d["genome1"], d["genome2"]))
+                keep += [g1, g2]
+                arr[i] = PairRow(d["key1"], d["key2"], g1, g2, d["n_masks"], d["sum_prefix"])
+            h = C.c_void_p()
+            st = L.lm_pairs_from_rows(arr, len(rows), None, C.byref(h))
+            if st != 0:
+                raise RuntimeError("lm_pairs_from_rows: status %d" % st)
+            handles.append(h)
+        hs = (C.c_void_p * max(len(handles), 1))(*[h.value for h in handles])
+        st = L.lm_pairs_merge(hs, len(handles), C.byref(merged))
+        if st == 7:
+            raise ValueError(L.lm_last_error(None).decode())
+        if st != 0:
+            raise RuntimeError("lm_pairs_merge: status %d" % st)
+        rows_p = C.POINTER(PairRow)()
+        nr = L.lm_pairs_rows(merged, C.byref(rows_p))
+        return [{f[0]: getattr(rows_p[i], f[0]) for f in PairRow._fields_} for i in range(nr)]
+    finally:
+        for h in handles:
+            L.lm_pairs_free(h)
+        if merged:
+            L.lm_pairs_free(merged)
 
 
 class Subseqs:
