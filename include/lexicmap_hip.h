@@ -546,7 +546,8 @@ typedef struct lm_stage_stats { /* measured work per batch (H, A
     int64_t anchors_cleared;   /* A: anchors after de-duplication */
     int64_t chains;            /* C: chains sent to alignment */
     int64_t window_bases;      /* sum of target window lengths */
-    int64_t pa_anchors;        /* pseudo-alignment anchors */
+    int64_t pa_anchors;        /* pseudo-alignment anchors EMITTED: without those nested in the anchor of the neighbouring
+                                  window position, which ClearSubstrPairs would drop (LM_PA_DROP_NESTED=0: every anchor) */
     int64_t hsps_aligned;      /* WFA problems */
     int64_t wfa_retries;
     int64_t rows;              /* HSP rows emitted */

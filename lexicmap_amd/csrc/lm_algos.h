@@ -1441,6 +1441,89 @@ LM_HD int lm_tree_search_first_tab(const uint64_t *keys, int n, uint64_t key, in
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Pseudo-alignment anchors that ClearSubstrPairs is certain to drop (k_pa_search skips them).
+//
+// lm_clear_sorted drops anchor v iff an anchor c that sorts earlier has c.qbegin >= v.qend - K, v.qend <= c.qend,
+// v.tbegin >= c.tbegin and v.tend <= c.tend; containers are taken from the raw list (a dropped anchor still drops others)
+// and strands are not compared.  Taking a dropped anchor v out of the raw list changes no other anchor's fate: whatever v
+// contains, v's own container c contains too, c sorts before it, and c.qbegin >= v.qend - K >= u.qend - K for every u
+// inside v.  So an anchor may be skipped whenever a container of it is known to be emitted in the same run, and the
+// container is the anchor of the NEIGHBOURING window position in the same exact-match run:
+//   forward strand: anchor (q = x, len = lp, t = i); container (x-1, lp+1, i-1), smaller QBegin, x-1 >= x+lp-K iff lp < K
+//   reverse strand: anchor (q = x+K-lp, lp, t = i+K-lp) from query position x; container from (x+1, i+1): same QBegin and
+//                   TBegin, length lp+1 (longer QEnd sorts first)
+// The container is emitted iff all of the conditions below hold; `false` (keep the anchor) is always safe.
+//
+// The values of the comparison index carry what the query side of the test needs above the position (positions stay
+// below 2^27, lm_pack_anchor): for the entry of query position x,
+//   strand 0: k-mer x-1 is indexed (exists, not dropped by the low-complexity filter) and the base x-1
+//   strand 1: k-mer x+1 is indexed and the base x+K
+#define LM_CMP_POS_MASK 0x0fffffffu /* position << 1 | strand */
+#define LM_CMP_NB_SHIFT 28          /* bit 28: the neighbouring k-mer is indexed; bits 29-30: the neighbouring base */
+LM_HD uint32_t lm_cmp_val(uint32_t pos, uint32_t strand, bool nb_indexed, uint32_t nb_base) {
+    return (pos << 1) | strand | ((uint32_t)(nb_indexed ? 1u : 0u) << LM_CMP_NB_SHIFT) | ((nb_base & 3u) << (LM_CMP_NB_SHIFT + 1));
+}
+// both values of query position `pos` (of npos): q = the query's bases (ASCII), fwd = its k-mer at pos (k_extract_kmers)
+LM_HD void lm_cmp_vals(const uint8_t *q, int pos, int64_t npos, int K, uint64_t fwd, uint32_t *v0, uint32_t *v1) {
+    const bool hp = pos >= 1, hn = (int64_t)pos + 1 < npos;
+    const uint32_t bprev = hp ? lm_base2bit(q[pos - 1]) : 0u, bnext = hn ? lm_base2bit(q[pos + K]) : 0u;
+    const uint64_t kprev = ((uint64_t)bprev << ((K - 1) << 1)) | (fwd >> 2), knext = ((fwd << 2) | bnext) & lm_kmer_mask(K);
+    *v0 = lm_cmp_val((uint32_t)pos, 0u, hp && !(kprev == 0 || lm_low_complexity(kprev, K)), bprev);
+    *v1 = lm_cmp_val((uint32_t)pos, 1u, hn && !(knext == 0 || lm_low_complexity(knext, K)), bnext);
+}
+// The k-mer at base `pos` of a 2-bit packed genome (4 bases per byte, first base in the top bits; two aligned 64-bit words,
+// the store is padded so that the second exists) as the window sees it - `wrc`: the window is the reverse complement of the
+// genome range, the k-mer at `pos` is then its `rc` - and the window bases next to it, before (wprev) and after (wnext) the
+// window k-mer, where the two words hold them (-1 where not: the base before a k-mer that starts a word, one in 32).
+LM_HD void lm_kmer_nb_from_bits(const uint8_t *gbits, int64_t goff, int pos, int K, bool wrc, uint64_t *kmer, uint64_t *rc,
+                                int *wprev, int *wnext) {
+    const int64_t byte = goff + (pos >> 2);
+    const uint64_t *p = (const uint64_t *)(gbits + (byte & ~7ll));
+    const uint64_t H = __builtin_bswap64(p[0]), L = __builtin_bswap64(p[1]);
+    const int o = (int)(byte & 7) * 8 + (pos & 3) * 2; // 0..62, even
+    const uint64_t v = o ? ((H << o) | (L >> (64 - o))) : H; // 32 bases from `pos`, left aligned
+    const uint64_t g = v >> (64 - 2 * K);
+    const int gprev = o ? (int)((H >> (64 - o)) & 3ull) : -1;
+    const int gnext = K < 32 ? (int)((v >> (62 - 2 * K)) & 3ull) : -1;
+    if (wrc) {
+        *rc = g;
+        *kmer = lm_revcomp(g, K);
+        *wprev = gnext < 0 ? -1 : 3 - gnext;
+        *wnext = gprev < 0 ? -1 : 3 - gprev;
+    } else {
+        *kmer = g;
+        *rc = lm_revcomp(g, K);
+        *wprev = gprev;
+        *wnext = gnext;
+    }
+}
+// rcs: the reverse-strand search of window position i (of npos); p: the task's minimum prefix; lp: the anchor's length;
+// wk: the window k-mer at i (window orientation, forward); wb: the window base i-1 (forward) or i+K (reverse) as 2 bits,
+// < 0 when the caller does not have it; qnb: the matched index value >> LM_CMP_NB_SHIFT; pp: the anchor's QBegin;
+// qb: the task's QBegin bound.
+// The rule in two halves, so that k_pa_search evaluates the window's once per candidate and the match's once per match.
+// Window side: `wb` when the neighbouring window position exists (2) and its k-mer passes k_pa_search's low-complexity
+// test (4), else -1.
+LM_HD int lm_pa_nested_window(bool rcs, int K, int i, int npos, uint64_t wk, int wb) {
+    if (wb < 0) return -1;
+    if (rcs ? i + 1 > npos - 1 : i < 1) return -1; // (2)
+    const uint64_t nk = rcs ? ((wk << 2) | (uint64_t)wb) & lm_kmer_mask(K) : ((uint64_t)wb << ((K - 1) << 1)) | (wk >> 2);
+    // (4) not aaa, ccc, ggg or ttt: some base of the neighbouring window k-mer differs from the next one
+    return ((nk ^ (nk >> 2)) & (lm_kmer_mask(K) >> 2)) != 0 ? wb : -1;
+}
+// Match side: `wbok` = the result of lm_pa_nested_window.
+LM_HD bool lm_pa_nested_match(bool rcs, int K, int p, int lp, int wbok, uint32_t qnb, int pp, int qb) {
+    if (wbok < 0) return false;
+    if (lp >= K || lp + 1 < p) return false;          // (1) the neighbour's match is one base longer, found by the normal rule
+    if (!(qnb & 1u)) return false;                    // (5) the neighbouring query k-mer is in the index
+    if ((int)((qnb >> 1) & 3u) != wbok) return false; // (3) the run goes on by one base
+    return rcs || pp - 1 >= qb; // (6) forward: the container's QBegin (its QEnd is the anchor's); reverse: the anchor's own test
+}
+LM_HD bool lm_pa_anchor_nested(bool rcs, int K, int p, int lp, int i, int npos, uint64_t wk, int wb, uint32_t qnb, int pp, int qb) {
+    return lm_pa_nested_match(rcs, K, p, lp, lm_pa_nested_window(rcs, K, i, npos, wk, wb), qnb, pp, qb);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // WFA, gap-affine (x=4,o=6,e=2), end-to-end, wf-adaptive(10,50,1), WFA2 backtrace priority — one work item.
 // Restates github.com/shenwei356/wfa v0.5.0 as used at lib-index-search.go:1910-1911,2261,2528 (not in the reference
 // tree): pattern = query (v), text = target (h), k = h - v, offset = h; 'I' consumes target, 'D' consumes query;

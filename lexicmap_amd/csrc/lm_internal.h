@@ -477,6 +477,7 @@ struct lm_tune {
     int chain1_wave = 1;     // seed chaining of pairs with many anchors by a wavefront each (k_chain1_wave); LM_CHAIN1_WAVE=0: every pair by one lane of k_chain1
     int pa_filter_roll = 1;  // k_pa_filter: a lane takes consecutive window positions (immediate funnel shifts over its own 64-base string); LM_PA_FILTER_ROLL=0: every 64th position, words passed between lanes
     int pa_seg_by_group = 1; // candidate segments by task group + XCD-local k_pa_search
+    int pa_drop_nested = 1;  // k_pa_search does not emit anchors nested in their neighbour's, which ClearSubstrPairs would drop (lm_pa_anchor_nested); LM_PA_DROP_NESTED=0: every anchor
     int wfa_resident_pct = 100; // share of the CUs' wavefront slots / LDS the persistent WFA kernels take (75 / 50 % measured in round 3: no gain / -20 %)
     int arena_reserve_pct = 90; // LM_ARENA_RESERVE_PCT: share of the scratch budget cut into the two lane slabs when a production-size index is opened, else at the first search (LaneSlabs; 0: slabs on demand as in round 4)
     int two_lanes = 1;       // two parts of a batch searched side by side, each with half of the scratch budget (LM_TWO_LANES=0: one after the other)
@@ -499,6 +500,7 @@ struct lm_tune {
         if (const char *e = getenv("LM_TWO_LANES")) two_lanes = atoi(e) != 0;
         if (const char *e = getenv("LM_ARENA_RESERVE_PCT")) arena_reserve_pct = std::max(0, std::min(100, atoi(e)));
         if (const char *e = getenv("LM_PA_FILTER_ROLL")) pa_filter_roll = atoi(e) != 0;
+        if (const char *e = getenv("LM_PA_DROP_NESTED")) pa_drop_nested = atoi(e) != 0;
     }
 };
 

@@ -94,8 +94,12 @@ __global__ void k_extract_kmers(const uint8_t *__restrict__ qseq, const int64_t 
             filtered = fwd == 0 || lm_low_complexity(fwd, K);
             keys_cmp[2 * i] = filtered ? (1ull << 63) : fwd;
             keys_cmp[2 * i + 1] = filtered ? (1ull << 63) : rc;
-            vals_cmp[2 * i] = (uint32_t)pos << 1;
-            vals_cmp[2 * i + 1] = ((uint32_t)pos << 1) | 1u;
+            // above the position: is the neighbouring k-mer of the same exact-match run indexed, and the base it adds
+            // (lm_pa_anchor_nested: the forward strand looks at position pos-1, the reverse strand at pos+1)
+            uint32_t v0, v1;
+            lm_cmp_vals(qseq + qoff[q], pos, posoff[q + 1] - posoff[q], K, fwd, &v0, &v1);
+            vals_cmp[2 * i] = v0;
+            vals_cmp[2 * i + 1] = v1;
         }
         // the 64 positions of a wavefront nearly always belong to one query: one atomic for all of them (one per position
         // was ~20 M atomics on ~1000 addresses per C3 part - most of the kernel's 23 ms)
@@ -998,6 +1002,14 @@ __device__ __forceinline__ void pa_kmer(const Task &t, const uint8_t *__restrict
     }
 }
 
+// pa_kmer for a packed genome, and the window bases next to the k-mer - i-1 and i+K in window orientation - where the two
+// words in hand hold them (lm_kmer_nb_from_bits; -1 where not).  Only meaningful for neighbours inside the window
+// (lm_pa_anchor_nested asks for no other).
+__device__ __forceinline__ void pa_kmer_nb(const Task &t, const uint8_t *__restrict__ gbits, int64_t goff, int i, int K,
+                                           uint64_t *kmer, uint64_t *rc, int *wprev, int *wnext) {
+    lm_kmer_nb_from_bits(gbits, goff, t.rc ? t.tBegin + t.wlen - K - i : t.tBegin + i, K, t.rc != 0, kmer, rc, wprev, wnext);
+}
+
 // The first P bases (P <= 16) of the window k-mer at position i and of its reverse complement, straight from the packed
 // genome: all the per-position test of k_pa_filter needs (11-base filter prefix + the bases [7, P) of the
 // partial-prefix rule). About half the arithmetic of building both full k-mers.
@@ -1454,7 +1466,10 @@ __global__ __launch_bounds__(256) void k_pa_search(DevIndexView ix, const Task *
                                                     int blocks_per_seg, const uint64_t *__restrict__ cand_all,
                                                     unsigned long long *__restrict__ count, int64_t cap,
                                                     uint64_t *__restrict__ outA, uint64_t *__restrict__ outB, int qbits,
-                                                    int tbits, int nseg, int xcd_map, unsigned long long *__restrict__ dbg) {
+                                                    int tbits, int nseg, int xcd_map, int drop_nested,
+                                                    unsigned long long *__restrict__ dbg) {
+    // drop_nested: anchors that ClearSubstrPairs is certain to drop because the neighbouring window position emits their
+    // container are not emitted (lm_pa_anchor_nested, lm_algos.h; tasks with a packed genome only).
     // qbits > 0: compact single-key anchors, task | QBegin:qbits | (32-Len):6 | TBegin:tbits | 2 flags in one u64 (outA is
     // not written): same order as (task, B) and one keys-only radix sort over the bits in use instead of two pair sorts.
     // qbits == 0 (batches whose fields need more than 64 bits): (task, B) pairs, the task staged beside B.
@@ -1500,9 +1515,10 @@ __global__ __launch_bounds__(256) void k_pa_search(DevIndexView ix, const Task *
     const int64_t stride = (int64_t)blocks_per_seg * blockDim.x;
     for (int64_t base = (int64_t)sub * blockDim.x; base < nc; base += stride) { // whole wavefronts stay together
         const int64_t ci = base + threadIdx.x;
-        unsigned long long d_0 = 0, d_1 = 0, d_it = 0, d_an = 0;
+        unsigned long long d_0 = 0, d_1 = 0, d_it = 0, d_an = 0, d_ne = 0;
         if (dbg) d_0 = wall_clock64();
         int j = 0, hi = 0, i = 0;
+        int nb = -1, pmin = 0; // the window's half of the nested-anchor rule (-1: keep every anchor), the task's minimum prefix
         bool rcs = false;
         uint64_t key = 0, right = 0;
         int64_t ti = 0;
@@ -1518,14 +1534,21 @@ __global__ __launch_bounds__(256) void k_pa_search(DevIndexView ix, const Task *
             const uint8_t *gb = t.g >= 0 ? (SRC ? src[ti].base : ix.gbits) : nullptr;
             const int64_t goff = t.g >= 0 ? (SRC ? src[ti].off : ix.g_off[t.g]) : 0;
             uint64_t kmer, rc;
-            pa_kmer(t, wbuf + t.woff, gb, goff, i, K, &kmer, &rc);
+            pmin = pa_min_prefix(min_prefix, t.wlen);
+            if (gb && (drop_nested || dbg)) {
+                int wprev, wnext;
+                pa_kmer_nb(t, gb, goff, i, K, &kmer, &rc, &wprev, &wnext);
+                nb = lm_pa_nested_window(rcs, K, i, t.wlen - K + 1, kmer, rcs ? wnext : wprev);
+            } else {
+                pa_kmer(t, wbuf + t.woff, gb, goff, i, K, &kmer, &rc);
+            }
             key = rcs ? rc : kmer;
             keys = keys_cmp + 2 * posoff[t.q];
             vals = vals_cmp + 2 * posoff[t.q];
             qb = (uint32_t)t.qBegin;
             qe = (uint32_t)t.qEnd;
             const bool lowc = kmer == 0 || kmer == ccc || kmer == ggg || kmer == ttt; // lib-seq_compare.go:374
-            if (lowc || !lm_tree_search_first_tab(keys, nvalid[t.q], key, pa_min_prefix(min_prefix, t.wlen), K,
+            if (lowc || !lm_tree_search_first_tab(keys, nvalid[t.q], key, pmin, K,
                                                   cmp_tab + tab_off[t.q], tab_bits[t.q], &j, &hi,
                                                   &right))
                 j = hi = 0;
@@ -1547,18 +1570,24 @@ __global__ __launch_bounds__(256) void k_pa_search(DevIndexView ix, const Task *
             if (live) {
                 const uint32_t v = vals[j];
                 const uint32_t lp = (uint32_t)lm_lcp(kj, key, K);
+                const uint32_t x = (v & LM_CMP_POS_MASK) >> 1; // (the bits above: the neighbouring k-mer, lm_cmp_val)
+                uint32_t pp;
                 if (!rcs) {
-                    const uint32_t pp = v >> 1;
+                    pp = x;
                     if (!((v & 1u) == 1u || pp < qb || pp + lp > qe)) {
                         ok = true;
                         B = lm_pack_anchor((int)pp, (int)lp, i, false, false);
                     }
                 } else {
-                    const uint32_t pp = (v >> 1) + (uint32_t)K - lp;
+                    pp = x + (uint32_t)K - lp;
                     if (!((v & 1u) == 0u || pp + lp < qb || pp > qe)) {
                         ok = true;
                         B = lm_pack_anchor((int)pp, (int)lp, i + K - (int)lp, true, true);
                     }
+                }
+                if (ok && lm_pa_nested_match(rcs, K, pmin, (int)lp, nb, v >> LM_CMP_NB_SHIFT, (int)pp, (int)qb)) {
+                    if (dbg) d_ne++;
+                    if (drop_nested) ok = false;
                 }
                 j++;
             }
@@ -1580,8 +1609,10 @@ __global__ __launch_bounds__(256) void k_pa_search(DevIndexView ix, const Task *
                 if (n_stg > PAS_STAGE - 64) flush(); // LDS accesses of one wavefront complete in program order
             }
         }
-        if (dbg) { // LM_DEBUG_PA_SEARCH: {candidates, wavefront passes, enumeration passes, anchors, clocks of the search, of the enumeration}
+        if (dbg) { // LM_DEBUG_PA_SEARCH: {candidates, wavefront passes, enumeration passes, anchors emitted, clocks of the search, of the
+                   // enumeration, anchors that satisfy the nested-anchor rule (emitted or not)}
             const unsigned long long nc_w = (unsigned long long)__popcll(__ballot(ci < nc)), d_2 = wall_clock64();
+            for (int o = 32; o > 0; o >>= 1) d_ne += __shfl_xor(d_ne, o, 64);
             if (lane == 0) {
                 atomicAdd(dbg + 0, nc_w);
                 atomicAdd(dbg + 1, 1ull);
@@ -1589,6 +1620,7 @@ __global__ __launch_bounds__(256) void k_pa_search(DevIndexView ix, const Task *
                 atomicAdd(dbg + 3, d_an);
                 atomicAdd(dbg + 4, d_1 - d_0);
                 atomicAdd(dbg + 5, d_2 - d_1);
+                atomicAdd(dbg + 6, d_ne);
             }
         }
     }
@@ -1734,6 +1766,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8))) void k_
             atomicAdd(dbg + 4 + 3 * cls, 1ull);
             atomicAdd(dbg + 5 + 3 * cls, (unsigned long long)n);
             atomicAdd(dbg + 6 + 3 * cls, d_3 - d_0);
+            atomicAdd(dbg + 16 + cls, (unsigned long long)(pa_off[ti + 1] - pa_off[ti])); // the anchors the window came with
         }
     }
 }
@@ -2699,7 +2732,7 @@ void launch_pa_search(hipStream_t st, DevIndexView ix, const Task *tasks, const 
                       const int64_t *tab_off, const int32_t *tab_bits, int K, int min_prefix,
                       const unsigned long long *seg_count, int nseg, int64_t seg_cap, const uint64_t *cand,
                       unsigned long long *count, int64_t cap, uint64_t *outA, uint64_t *outB, int qbits, int tbits,
-                      int xcd_map) {
+                      int xcd_map, bool drop_nested) {
     // the candidate counts are only known on the device: a fixed number of blocks per segment.  xcd_map (segments in query
     // order, k_pa_filter's seg_by_group): as many blocks per range of segments as one XCD holds (32 CUs x 8), so that an XCD
     // works on one or two ranges - a few queries - at a time; otherwise a grid that just fills the chip.
@@ -2713,13 +2746,15 @@ void launch_pa_search(hipStream_t st, DevIndexView ix, const Task *tasks, const 
     if (ps_dbg && d_dbg) (void)hipMemsetAsync(d_dbg, 0, 8 * sizeof(unsigned long long), st);
     hipLaunchKernelGGL(src ? k_pa_search<true> : k_pa_search<false>, dim3(nseg8 * bps), dim3(256), 0, st, ix, tasks, src, wbuf, keys_cmp, vals_cmp, posoff, nvalid, cmp_tab,
                        tab_off, tab_bits, K, min_prefix, seg_count, seg_cap, bps, cand, count, cap, outA, outB, qbits, tbits, nseg,
-                       xcd_map, ps_dbg ? d_dbg : nullptr);
+                       xcd_map, drop_nested ? 1 : 0, ps_dbg ? d_dbg : nullptr);
     if (ps_dbg && d_dbg) {
         unsigned long long h[8] = {0};
         (void)hipStreamSynchronize(st);
         (void)hipMemcpy(h, d_dbg, sizeof h, hipMemcpyDeviceToHost);
-        fprintf(stderr, "[lm] k_pa_search: %llu candidates in %llu wavefront passes (%.1f per pass), %llu enumeration passes, %llu anchors (%.2f per enumeration pass), wavefront-ms: search %.1f, enumeration %.1f\n",
-                h[0], h[1], h[1] ? (double)h[0] / (double)h[1] : 0.0, h[2], h[3], h[2] ? (double)h[3] / (double)h[2] : 0.0, (double)h[4] / 1e5, (double)h[5] / 1e5);
+        const unsigned long long found = h[3] + (drop_nested ? h[6] : 0ull); // (a nested anchor is emitted only with the rule off)
+        fprintf(stderr, "[lm] k_pa_search: %llu candidates in %llu wavefront passes (%.1f per pass), %llu enumeration passes, %llu anchors (%.2f per enumeration pass), wavefront-ms: search %.1f, enumeration %.1f; %llu anchors found, %llu nested in their neighbour's (%.1f %%, %s)\n",
+                h[0], h[1], h[1] ? (double)h[0] / (double)h[1] : 0.0, h[2], h[3], h[2] ? (double)h[3] / (double)h[2] : 0.0, (double)h[4] / 1e5, (double)h[5] / 1e5,
+                found, h[6], found ? 100.0 * (double)h[6] / (double)found : 0.0, drop_nested ? "not emitted" : "emitted");
     }
 }
 void launch_pa_task_off_sorted(hipStream_t st, const uint64_t *sortedA, int shift, int64_t total, int64_t ntasks,
@@ -2731,20 +2766,21 @@ void launch_pa_chain(hipStream_t st, const uint64_t *B, const int64_t *pa_off, i
                      int32_t *clr_n, int qbits, int tbits) {
     int g = (int)(ntasks < 1 ? 1 : (ntasks > 262144 ? 262144 : ntasks));
     static const bool pa_dbg = getenv("LM_DEBUG_PA_CHAIN") != nullptr; // phase times of k_pa_chain_wave
-    static unsigned long long *d_pa_dbg = nullptr; // (its own small buffer: 16 counters)
-    if (pa_dbg && !d_pa_dbg && hipMalloc((void **)&d_pa_dbg, 16 * sizeof(unsigned long long)) != hipSuccess) d_pa_dbg = nullptr;
+    static unsigned long long *d_pa_dbg = nullptr; // (its own small buffer: 20 counters)
+    if (pa_dbg && !d_pa_dbg && hipMalloc((void **)&d_pa_dbg, 20 * sizeof(unsigned long long)) != hipSuccess) d_pa_dbg = nullptr;
     unsigned long long *dbg = pa_dbg ? d_pa_dbg : nullptr;
-    if (dbg) (void)hipMemsetAsync(dbg, 0, 16 * sizeof(unsigned long long), st);
+    if (dbg) (void)hipMemsetAsync(dbg, 0, 20 * sizeof(unsigned long long), st);
     hipLaunchKernelGGL(k_pa_chain_wave, dim3(g), dim3(64), 0, st, B, pa_off, ntasks, K, opt, subs, marks, msi, stack, out, out_n,
                        clr_n, qbits, tbits, dbg);
     if (dbg) {
-        unsigned long long h[16] = {0};
+        unsigned long long h[20] = {0};
         (void)hipStreamSynchronize(st);
         (void)hipMemcpy(h, dbg, sizeof h, hipMemcpyDeviceToHost);
         fprintf(stderr, "[lm] k_pa_chain: %lld windows (%llu with a DP), wavefront-ms: clear+trim %.1f, DP %.1f, backtrack %.1f; "
-                        "by anchors left {windows, anchors, wavefront-ms}: 2-8 {%llu, %llu, %.1f} 9-64 {%llu, %llu, %.1f} 65-256 {%llu, %llu, %.1f} 257+ {%llu, %llu, %.1f}\n",
-                (long long)ntasks, h[3], (double)h[0] / 1e5, (double)h[1] / 1e5, (double)h[2] / 1e5, h[4], h[5], (double)h[6] / 1e5, h[7], h[8],
-                (double)h[9] / 1e5, h[10], h[11], (double)h[12] / 1e5, h[13], h[14], (double)h[15] / 1e5);
+                        "by anchors left {windows, anchors, wavefront-ms, anchors before clear}: 2-8 {%llu, %llu, %.1f, %llu} 9-64 {%llu, %llu, %.1f, %llu} "
+                        "65-256 {%llu, %llu, %.1f, %llu} 257+ {%llu, %llu, %.1f, %llu}\n",
+                (long long)ntasks, h[3], (double)h[0] / 1e5, (double)h[1] / 1e5, (double)h[2] / 1e5, h[4], h[5], (double)h[6] / 1e5, h[16], h[7], h[8],
+                (double)h[9] / 1e5, h[17], h[10], h[11], (double)h[12] / 1e5, h[18], h[13], h[14], (double)h[15] / 1e5, h[19]);
     }
 }
 void launch_gather_chain2(hipStream_t st, const LmChain2 *in, const int64_t *pa_off, const int32_t *out_n,

@@ -1952,7 +1952,7 @@ static void run_pseudo(AlignCtx &a, TaskSpan ht, std::vector<int64_t> &res_off_h
     a.pa_count.ensure(2 + LM_PA_MAX_SEGS); // anchors, the filter's group counter, candidates per segment
     if (a.pa_cap < (int64_t)1 << 20) a.pa_cap = std::max<int64_t>((int64_t)1 << 20, W / 8);
     if (const char *e = getenv("LM_DEBUG_PA_CAP")) a.pa_cap = std::max<int64_t>(1, atoll(e)); // test hook: force the re-run
-    int64_t TP = 0;
+    int64_t TP = 0, NC = 0; // anchors, candidates of the chunk
     int nseg = 1;
     // candidate segments by task-group range + XCD-local search pay when a query's comparison tables (12 B per k-mer and
     // strand + the bucket table) are a sizeable part of an XCD's 4-MB L2: long reads.  For gene-sized queries (tables of tens of
@@ -1998,7 +1998,7 @@ static void run_pseudo(AlignCtx &a, TaskSpan ht, std::vector<int64_t> &res_off_h
             launch_pa_search(S(ix), ix->view, tasks_d, src_d, a.wb, a.w->k_cmp, a.w->v_cmp, qb->posoff_cmp(), a.w->nvalid.p,
                              a.w->cmp_tab.p, qb->d_tab_off.p, qb->d_tab_bits.p, LM_CMP_K, 11, a.pa_count.p + 2, nseg, seg_cap,
                              a.B1.p, a.pa_count.p, a.pa_cap, a.A0.p, a.B0.p, compact ? qbits : 0, compact ? tbits : 0,
-                             by_group ? 1 : 0);
+                             by_group ? 1 : 0, ix->tune.pa_drop_nested != 0);
         }
         std::vector<unsigned long long> hv((size_t)2 + nseg);
         HIPCHK(hipMemcpyAsync(hv.data(), a.pa_count.p, hv.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, S(ix)));
@@ -2020,6 +2020,7 @@ static void run_pseudo(AlignCtx &a, TaskSpan ht, std::vector<int64_t> &res_off_h
                 }
             prof_add_bytes(ix, "k_pa_search", 8 * std::min<int64_t>(ncand, a.pa_cap) + 8 * std::min<int64_t>(TP, a.pa_cap) + idx);
         }
+        NC = ncand;
         dbg_stamp("pseudo-alignment anchors of a chunk done");
         if (getenv("LM_DEBUG"))
             fprintf(stderr, "[lm] pseudo-alignment: %lld window bases, %lld candidates (fullest of %d segments: %lld of %lld), %lld anchors\n",
@@ -2046,9 +2047,13 @@ static void run_pseudo(AlignCtx &a, TaskSpan ht, std::vector<int64_t> &res_off_h
     }
     // anchors per window byte of what has been seen (sizes the next chunks so that they need no halving); small chunks
     // (the odd tasks left behind a halving) say little
-    if (W > ((int64_t)64 << 20)) *a.pa_ratio = std::max(*a.pa_ratio * 0.9, (double)TP / (double)W);
-    else if (W > 0 && *a.pa_ratio == 0) *a.pa_ratio = (double)TP / (double)W;
-    if (TP >= (int64_t)1 << 31 || (BUDGET(ix) > 0 && TP * 90 > BUDGET(ix) * 13 / 100)) {
+    // Of the ~90 bytes of scratch per anchor, 16 (the two key buffers) are sized by the larger of anchors and candidates.  With
+    // the nested anchors gone (lm_tune::pa_drop_nested) a chunk can hold more candidates than anchors: what the candidates
+    // take beyond the anchors is counted in anchors' worth, so that chunks are sized by the memory they need.
+    const int64_t TPm = TP + std::max<int64_t>(0, NC - TP) * 16 / 90;
+    if (W > ((int64_t)64 << 20)) *a.pa_ratio = std::max(*a.pa_ratio * 0.9, (double)TPm / (double)W);
+    else if (W > 0 && *a.pa_ratio == 0) *a.pa_ratio = (double)TPm / (double)W;
+    if (TP >= (int64_t)1 << 31 || (BUDGET(ix) > 0 && TPm * 90 > BUDGET(ix) * 13 / 100)) {
         if (nt <= 1) throw HipError("too many pseudo-alignment anchors for one chain window");
         a.stats->window_bases -= W; // the chunk comes back in halves
         throw ChunkTooLarge();
