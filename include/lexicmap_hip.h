@@ -799,6 +799,29 @@ typedef struct lm_chain2 {
 lm_status lm_pseudoalign_batch(lm_index *idx, const lm_query *queries, size_t nq, const lm_query *targets,
                                const uint32_t *qidx, const uint32_t *qbegin, const uint32_t *qend, size_t nproblems,
                                lm_stage **out, const int64_t **res_off, const lm_chain2 **res);
+/* The same, and the pseudo-alignment anchors the chains were made from: anchors[anchor_off[i] .. anchor_off[i+1]) are the
+ * anchors emitted for problem i (window coordinates), in the order of the sorted device list (the ClearSubstrPairs order:
+ * QBegin ascending, QEnd descending, TBegin ascending, strand flags). */
+lm_status lm_pseudoalign_batch_ex(lm_index *idx, const lm_query *queries, size_t nq, const lm_query *targets,
+                                  const uint32_t *qidx, const uint32_t *qbegin, const uint32_t *qend, size_t nproblems,
+                                  lm_stage **out, const int64_t **res_off, const lm_chain2 **res,
+                                  const int64_t **anchor_off, const lm_anchor **anchors);
+/* The same for windows of the RESIDENT genomes: problem i compares queries[query] over [qbegin, qend] with the wlen bases
+ * from base tbegin of local genome `local_genome` (concatenated-genome coordinates, as lm_index_fetch), turned into their
+ * reverse complement when rc != 0.  The windows are read from the 2-bit genomes by the kernels a search runs (a search
+ * never takes the ASCII path of lm_pseudoalign_batch), on a handle with host-resident genomes through its staging buffer.
+ * LM_ERR_ARG with a text: a query or genome that does not exist here, tbegin < 0, wlen < 0, a window past the genome's last
+ * base, qend past the query.  All regions are one chunk: one that needs more anchors than the scratch budget allows is an
+ * error (LM_ERR_HIP), it is not split. */
+typedef struct lm_pa_region {
+    uint32_t query, qbegin, qend;
+    int32_t rc;
+    int64_t local_genome;
+    int32_t tbegin, wlen;
+} lm_pa_region;
+lm_status lm_pseudoalign_regions(lm_index *idx, const lm_query *queries, size_t nq, const lm_pa_region *regions,
+                                 size_t nregions, lm_stage **out, const int64_t **res_off, const lm_chain2 **res,
+                                 const int64_t **anchor_off, const lm_anchor **anchors);
 
 /* wfa.Aligner.Align(q,t) with DefaultPenalties, global, AdaptiveReduction(DefaultAdaptiveOption)
  * (lib-index-search.go:1910-1911,2261,2528). ops CSR: op<<32|n in forward order. */

@@ -76,6 +76,15 @@ class Chain2(C.Structure):
                 ("aligned_bases_t", C.c_int32), ("pident", C.c_double)]
 
 
+LM_ERR_ARG = 7  # lm_status
+
+
+class PaRegion(C.Structure):
+    """lm_pa_region: one window of a resident genome for Index.pseudoalign_regions"""
+    _fields_ = [("query", C.c_uint32), ("qbegin", C.c_uint32), ("qend", C.c_uint32), ("rc", C.c_int32),
+                ("local_genome", C.c_int64), ("tbegin", C.c_int32), ("wlen", C.c_int32)]
+
+
 class Wfa(C.Structure):
     _fields_ = [("status", C.c_int32), ("score", C.c_int32), ("qbegin", C.c_int32), ("qend", C.c_int32),
                 ("tbegin", C.c_int32), ("tend", C.c_int32), ("align_len", C.c_uint32), ("matches", C.c_uint32),
@@ -264,6 +273,11 @@ def lib():
     L.lm_pseudoalign_batch.argtypes = [vp, C.POINTER(Query), C.c_size_t, C.POINTER(Query), C.POINTER(C.c_uint32),
                                        C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(vp),
                                        C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.POINTER(Chain2))]
+    L.lm_pseudoalign_batch_ex.argtypes = L.lm_pseudoalign_batch.argtypes + [C.POINTER(C.POINTER(C.c_int64)),
+                                                                            C.POINTER(C.POINTER(Anchor))]
+    L.lm_pseudoalign_regions.argtypes = [vp, C.POINTER(Query), C.c_size_t, C.POINTER(PaRegion), C.c_size_t, C.POINTER(vp),
+                                         C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.POINTER(Chain2)),
+                                         C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.POINTER(Anchor))]
     L.lm_wfa_batch.argtypes = [vp, C.POINTER(Query), C.POINTER(Query), C.c_size_t, C.POINTER(vp),
                                C.POINTER(C.POINTER(Wfa)), C.POINTER(C.POINTER(C.c_uint64))]
     L.lm_index_build_synthetic.argtypes = [C.POINTER(SynthSpec), C.POINTER(Options), C.c_int, C.POINTER(vp)]
@@ -998,6 +1012,60 @@ class Index:
         out = []
         for i in range(n):
             out.append([{f[0]: getattr(rv[j], f[0]) for f in Chain2._fields_} for j in range(ro[i], ro[i + 1])])
+        L.lm_stage_free(sg)
+        return out
+
+    @staticmethod
+    def _chains_and_anchors(n, ro, rv, ao, av):
+        import numpy as np
+        chains = [[{f[0]: getattr(rv[j], f[0]) for f in Chain2._fields_} for j in range(ro[i], ro[i + 1])] for i in range(n)]
+        off = [ao[i] for i in range(n + 1)]
+        rec = np.dtype([("qbegin", "<i4"), ("tbegin", "<i4"), ("len", "u1"), ("trc", "u1"), ("qrc", "u1"), ("pad", "u1")])
+        a = np.ctypeslib.as_array(C.cast(av, C.POINTER(C.c_uint8)), shape=(off[n] * C.sizeof(Anchor),)).view(rec) if off[n] else \
+            np.zeros(0, rec)
+        cols = list(zip(a["qbegin"].tolist(), a["tbegin"].tolist(), a["len"].tolist(), a["trc"].tolist(), a["qrc"].tolist()))
+        return chains, [cols[off[i]:off[i + 1]] for i in range(n)]
+
+    def pseudoalign_anchors(self, queries, problems):
+        """pseudoalign (ASCII windows of the caller), and per problem the emitted anchors (qbegin, tbegin, len, trc, qrc) in the
+        order of the sorted device list (lm_pseudoalign_batch_ex): (chains, anchors)"""
+        L = lib()
+        qarr, k1 = _queries(queries)
+        tarr, k2 = _queries([p[3] for p in problems])
+        n = len(problems)
+        qi = (C.c_uint32 * max(n, 1))(*[p[0] for p in problems])
+        qb = (C.c_uint32 * max(n, 1))(*[p[1] for p in problems])
+        qe = (C.c_uint32 * max(n, 1))(*[p[2] for p in problems])
+        sg, ro, rv = C.c_void_p(), C.POINTER(C.c_int64)(), C.POINTER(Chain2)()
+        ao, av = C.POINTER(C.c_int64)(), C.POINTER(Anchor)()
+        st = L.lm_pseudoalign_batch_ex(self.h, qarr, len(queries), tarr, qi, qb, qe, n, C.byref(sg), C.byref(ro), C.byref(rv),
+                                       C.byref(ao), C.byref(av))
+        if st != 0:
+            self._err(st)
+        out = self._chains_and_anchors(n, ro, rv, ao, av)
+        L.lm_stage_free(sg)
+        return out
+
+    def pseudoalign_regions(self, queries, regions):
+        """pseudo-alignment of windows of the resident genomes, through the kernels a search runs (lm_pseudoalign_regions).
+        regions: list of (query index, qbegin, qend, local genome, tbegin, wlen, rc) with tbegin in concatenated-genome
+        coordinates (as fetch).  Returns (chains, anchors) as pseudoalign_anchors.  A region the library refuses (LM_ERR_ARG)
+        raises ValueError with its text."""
+        L = lib()
+        qarr, k1 = _queries(queries)
+        n = len(regions)
+        arr = (PaRegion * max(n, 1))()
+        for i, (q, qb, qe, g, tb, wl, rc) in enumerate(regions):
+            arr[i] = PaRegion(q, qb, qe, int(rc), g, tb, wl)
+        sg, ro, rv = C.c_void_p(), C.POINTER(C.c_int64)(), C.POINTER(Chain2)()
+        ao, av = C.POINTER(C.c_int64)(), C.POINTER(Anchor)()
+        st = L.lm_pseudoalign_regions(self.h, qarr, len(queries), arr, n, C.byref(sg), C.byref(ro), C.byref(rv), C.byref(ao),
+                                      C.byref(av))
+        if st == LM_ERR_ARG:
+            raise ValueError(L.lm_last_error(self.h).decode())
+        if st != 0:
+            self._err(st)
+        out = self._chains_and_anchors(n, ro, rv, ao, av)
         L.lm_stage_free(sg)
         return out
 

@@ -1334,6 +1334,21 @@ LM_HD uint32_t lm_pa_bloom_slot(uint32_t pfx, int which, int blog) {
 LM_HD uint64_t lm_pa_bits_words(int log) {
     return 2 * ((uint64_t)1 << (log - 5)) + ((uint64_t)1 << (lm_pa_bloom_log(log) - 5)) + ((uint64_t)1 << (LM_PA_MAP9_LOG - 5));
 }
+// the size class of a query's filter, as the query upload sizes it: ~16 bits per entry of the comparison index (nk = both strands
+// of every k-mer position of the query, kept or not), 2^13 .. 2^24 bits
+LM_HD int lm_pa_filter_log(int64_t nk) {
+    int lg = 13;
+    while (lg < 24 && ((int64_t)1 << lg) < 16 * nk) lg++;
+    return lg;
+}
+#define LM_TAB_BITS_MIN 12 /* bucket table over the leading bits of a query's sorted k-mers: 2^12 .. 2^20 buckets */
+#define LM_TAB_BITS_MAX 20
+// bits of that bucket table: about two buckets per entry
+LM_HD int lm_cmp_tab_bits(int64_t nk) {
+    int tb = LM_TAB_BITS_MIN;
+    while (tb < LM_TAB_BITS_MAX && ((int64_t)1 << tb) < 2 * nk) tb++;
+    return tb;
+}
 LM_HD uint64_t lm_pa_bloom_word0(int log) { return 2 * ((uint64_t)1 << (log - 5)); }
 LM_HD uint64_t lm_pa_map9_word0(int log) { return lm_pa_bloom_word0(log) + ((uint64_t)1 << (lm_pa_bloom_log(log) - 5)); }
 // every bit a k-mer of the query sets (`or_bit(word index, mask)`: atomicOr on the device)

@@ -132,8 +132,7 @@ void launch_extract_windows(hipStream_t st, DevIndexView ix, const Task *tasks, 
 void launch_extract_windows_at(hipStream_t st, DevIndexView ix, const Task *tasks, const TaskSrc *src, const int32_t *idx,
                                const int64_t *dest, int64_t n, uint8_t *wbuf);
 void launch_stage_genome_bits(hipStream_t st, const StageCmd *cmds, int64_t n);
-#define LM_TAB_BITS_MIN 12 /* bucket table over the leading bits of a query's sorted k-mers: 2^12 .. 2^20 buckets */
-#define LM_TAB_BITS_MAX 20
+// (LM_TAB_BITS_MIN / _MAX, lm_algos.h: bucket table over the leading bits of a query's sorted k-mers, 2^12 .. 2^20 buckets)
 void launch_build_cmp_tab(hipStream_t st, const uint64_t *keys_cmp, const int64_t *posoff, const int32_t *nvalid, int nq,
                           int K, const int64_t *tab_off, const int32_t *tab_bits, int64_t tab_words, uint32_t *tab);
 void launch_sum_i32(hipStream_t st, const int32_t *v, int64_t n, unsigned long long *out);

@@ -1607,8 +1607,7 @@ static lm_qbatch *upload_part(lm_index *ix, const lm_query *queries, size_t nq, 
             std::vector<int32_t> blog(nq + 1, 13);
             for (size_t i = 0; i < nq; i++) {
                 const int64_t nk = 2 * (pc[i + 1] - pc[i]);
-                int lg = 13;
-                while (lg < 24 && ((int64_t)1 << lg) < 16 * nk) lg++;
+                const int lg = lm_pa_filter_log(nk);
                 blog[i] = lg;
                 boff[i + 1] = boff[i] + (int64_t)lm_pa_bits_words(lg);
             }
@@ -1617,8 +1616,7 @@ static lm_qbatch *upload_part(lm_index *ix, const lm_query *queries, size_t nq, 
             std::vector<int32_t> tbits(nq + 1, LM_TAB_BITS_MIN);
             for (size_t i = 0; i < nq; i++) { // about two buckets per k-mer
                 const int64_t nk = 2 * (pc[i + 1] - pc[i]);
-                int tb = LM_TAB_BITS_MIN;
-                while (tb < LM_TAB_BITS_MAX && ((int64_t)1 << tb) < 2 * nk) tb++;
+                const int tb = lm_cmp_tab_bits(nk);
                 tbits[i] = tb;
                 toff[i + 1] = toff[i] + ((int64_t)1 << tb) + 1;
             }
@@ -1746,6 +1744,10 @@ struct AlignCtx {
     double pa_ratio_own = 0, *pa_ratio = &pa_ratio_own; // anchors per window byte seen so far (shared by the two contexts)
     DBuf<int64_t> pa_off;
     DBuf<uint64_t> A0, B0, A1, B1;
+    // the sorted anchor list run_pseudo left behind (the stage-level entry points return it): pa_last_n anchors in (A0,) B0,
+    // the first of every task in pa_off; pa_last_qbits > 0: compact single keys with that many query / window bits
+    int64_t pa_last_n = 0;
+    int pa_last_qbits = 0, pa_last_tbits = 0;
     DBuf<LmSub> subs;
     DBuf<uint8_t> marks;
     DBuf<uint64_t> msi;
@@ -1918,6 +1920,7 @@ static void run_pseudo(AlignCtx &a, TaskSpan ht, std::vector<int64_t> &res_off_h
     int64_t nt = (int64_t)ht.size();
     res_off_h.assign(nt + 1, 0);
     res_h.clear();
+    a.pa_last_n = 0;
     if (nt == 0) return;
     int64_t W = ht.back().woff + ht.back().wlen - base;
     if (own_windows) {
@@ -2059,6 +2062,9 @@ static void run_pseudo(AlignCtx &a, TaskSpan ht, std::vector<int64_t> &res_off_h
         throw ChunkTooLarge();
     }
     a.stats->pa_anchors += TP;
+    a.pa_last_n = TP;
+    a.pa_last_qbits = compact ? qbits : 0;
+    a.pa_last_tbits = compact ? tbits : 0;
     a.pa_off.ensure((size_t)nt + 2);
     a.out_n.ensure((size_t)nt + 1);
     a.clr_n.ensure((size_t)nt + 1);
@@ -3970,10 +3976,42 @@ lm_status lm_seed_chain_batch(lm_index *ix, const lm_query *queries, size_t nq, 
     return LM_OK;
 }
 
-lm_status lm_pseudoalign_batch(lm_index *ix, const lm_query *queries, size_t nq, const lm_query *targets,
-                               const uint32_t *qidx, const uint32_t *qbegin, const uint32_t *qend, size_t nproblems,
-                               lm_stage **out, const int64_t **res_off, const lm_chain2 **resv) {
-    *out = nullptr;
+namespace lm {
+// The anchors of the chunk run_pseudo has just finished, per task, in the order of the sorted device list; compact single
+// keys (k_pa_search, qbits > 0) are decoded here.
+static void pa_anchors_to_host(AlignCtx &a, int64_t nt, std::vector<int64_t> &off, std::vector<lm_anchor> &out) {
+    lm_index *ix = a.ix;
+    off.assign((size_t)nt + 1, 0);
+    out.clear();
+    const int64_t TP = a.pa_last_n;
+    if (TP == 0) return;
+    std::vector<uint64_t> B;
+    d2h(ix, B, a.B0.p, (size_t)TP);
+    d2h(ix, off, a.pa_off.p, (size_t)nt + 1);
+    sync(ix);
+    const int qbits = a.pa_last_qbits, tbits = a.pa_last_tbits;
+    out.resize((size_t)TP);
+    for (int64_t i = 0; i < TP; i++) {
+        LmSub x;
+        if (qbits > 0) { // task | QBegin:qbits | (32 - Len):6 | TBegin:tbits | QRC | TRC
+            const uint64_t v = B[(size_t)i];
+            x.qbegin = (int32_t)((v >> (8 + tbits)) & (((uint64_t)1 << qbits) - 1));
+            x.len = (uint8_t)(32 - (int)((v >> (2 + tbits)) & 63));
+            x.tbegin = (int32_t)((v >> 2) & (((uint64_t)1 << tbits) - 1));
+            x.qrc = (uint8_t)((v >> 1) & 1);
+            x.trc = (uint8_t)(v & 1);
+        } else {
+            x = lm_unpack_anchor(B[(size_t)i]);
+        }
+        out[(size_t)i] = {x.qbegin, x.tbegin, x.len, x.trc, x.qrc, 0};
+    }
+}
+
+// The two pseudo-alignment seams: tasks `ht` in one chunk, chains and anchors into a new lm_stage.  packed: the windows are
+// ranges of the resident genomes (t.g >= 0), read as a search reads them; else ASCII windows `wb` of the caller.
+static lm_status pseudoalign_stage(lm_index *ix, const lm_query *queries, size_t nq, std::vector<Task> &ht, bool packed,
+                                   const std::vector<uint8_t> &wb, lm_stage **out, const int64_t **res_off, const lm_chain2 **resv,
+                                   const int64_t **anchor_off, const lm_anchor **anchors) {
     lm_qbatch *qb = nullptr;
     lm_status s = lm_qbatch_upload(ix, queries, nq, &qb);
     if (s != LM_OK) return s;
@@ -3988,39 +4026,28 @@ lm_status lm_pseudoalign_batch(lm_index *ix, const lm_query *queries, size_t nq,
         a.qb = qb;
         a.w = &w;
         a.stats = &st;
-        // explicit windows: upload targets as the window buffer, build tasks on the host
-        std::vector<Task> ht(nproblems);
-        int64_t off = 0;
-        for (size_t i = 0; i < nproblems; i++) {
-            Task t;
-            memset(&t, 0, sizeof t);
-            t.seg = (uint32_t)i;
-            t.q = qidx[i];
-            t.g = -1; // windows come from the caller, k_extract_windows skips them
-            t.bg = 0;
-            t.qBegin = (int32_t)qbegin[i];
-            t.qEnd = (int32_t)qend[i];
-            t.wlen = (int32_t)targets[i].len;
-            t.woff = off;
-            off += t.wlen;
-            ht[i] = t;
-        }
-        std::vector<uint8_t> wb((size_t)off + 64, 'A');
-        for (size_t i = 0; i < nproblems; i++)
-            if (targets[i].len) memcpy(&wb[(size_t)ht[i].woff], targets[i].seq, targets[i].len);
-        a.wbuf.ensure(wb.size());
-        HIPCHK(hipMemcpyAsync(a.wbuf.p, wb.data(), wb.size(), hipMemcpyHostToDevice, S(ix)));
         std::vector<int64_t> ro;
         std::vector<LmChain2> rv;
         TaskSpan sp;
         sp.p = ht.data();
         sp.n = ht.size();
-        run_pseudo(a, sp, ro, rv);
+        if (packed) {
+            try {
+                run_pseudo(a, sp, ro, rv, nullptr, 0, false);
+            } catch (const ChunkTooLarge &) {
+                throw HipError("too many pseudo-alignment anchors for one chunk of regions");
+            }
+        } else {
+            a.wbuf.ensure(wb.size());
+            HIPCHK(hipMemcpyAsync(a.wbuf.p, wb.data(), wb.size(), hipMemcpyHostToDevice, S(ix)));
+            run_pseudo(a, sp, ro, rv);
+        }
         sg->i64a = ro;
         sg->chains2.resize(rv.size());
         for (size_t i = 0; i < rv.size(); i++)
             sg->chains2[i] = {rv[i].qbegin, rv[i].qend, rv[i].tbegin, rv[i].tend, rv[i].nanchors, rv[i].matched_bases,
                               rv[i].aligned_bases_q, rv[i].aligned_bases_t, rv[i].pident};
+        if (anchor_off) pa_anchors_to_host(a, (int64_t)ht.size(), sg->i64b, sg->raw);
     } catch (const std::exception &e) {
         ix->err = e.what();
         delete sg;
@@ -4030,8 +4057,95 @@ lm_status lm_pseudoalign_batch(lm_index *ix, const lm_query *queries, size_t nq,
     lm_qbatch_free(qb);
     *res_off = sg->i64a.data();
     *resv = sg->chains2.data();
+    if (anchor_off) {
+        *anchor_off = sg->i64b.data();
+        *anchors = sg->raw.data();
+    }
     *out = sg;
     return LM_OK;
+}
+} // namespace lm
+
+lm_status lm_pseudoalign_batch_ex(lm_index *ix, const lm_query *queries, size_t nq, const lm_query *targets,
+                                  const uint32_t *qidx, const uint32_t *qbegin, const uint32_t *qend, size_t nproblems,
+                                  lm_stage **out, const int64_t **res_off, const lm_chain2 **resv,
+                                  const int64_t **anchor_off, const lm_anchor **anchors) {
+    if (out) *out = nullptr;
+    // (anchor_off and anchors: both or neither - lm_pseudoalign_batch passes neither)
+    if (!ix || !out || !res_off || !resv || (anchor_off == nullptr) != (anchors == nullptr) || (nproblems && (!targets || !qidx || !qbegin || !qend)))
+        return LM_ERR_ARG;
+    // explicit windows: the targets are the window buffer, the tasks are built on the host
+    std::vector<Task> ht(nproblems);
+    int64_t off = 0;
+    for (size_t i = 0; i < nproblems; i++) {
+        Task t;
+        memset(&t, 0, sizeof t);
+        t.seg = (uint32_t)i;
+        t.q = qidx[i];
+        t.g = -1; // windows come from the caller, k_extract_windows skips them
+        t.bg = 0;
+        t.qBegin = (int32_t)qbegin[i];
+        t.qEnd = (int32_t)qend[i];
+        t.wlen = (int32_t)targets[i].len;
+        t.woff = off;
+        off += t.wlen;
+        ht[i] = t;
+    }
+    std::vector<uint8_t> wb((size_t)off + 64, 'A');
+    for (size_t i = 0; i < nproblems; i++)
+        if (targets[i].len) memcpy(&wb[(size_t)ht[i].woff], targets[i].seq, targets[i].len);
+    return pseudoalign_stage(ix, queries, nq, ht, false, wb, out, res_off, resv, anchor_off, anchors);
+}
+
+lm_status lm_pseudoalign_batch(lm_index *ix, const lm_query *queries, size_t nq, const lm_query *targets,
+                               const uint32_t *qidx, const uint32_t *qbegin, const uint32_t *qend, size_t nproblems,
+                               lm_stage **out, const int64_t **res_off, const lm_chain2 **resv) {
+    return lm_pseudoalign_batch_ex(ix, queries, nq, targets, qidx, qbegin, qend, nproblems, out, res_off, resv, nullptr, nullptr);
+}
+
+lm_status lm_pseudoalign_regions(lm_index *ix, const lm_query *queries, size_t nq, const lm_pa_region *regions,
+                                 size_t nregions, lm_stage **out, const int64_t **res_off, const lm_chain2 **resv,
+                                 const int64_t **anchor_off, const lm_anchor **anchors) {
+    if (out) *out = nullptr;
+    if (!ix || !out || !res_off || !resv || !anchor_off || !anchors || (nregions && !regions)) return LM_ERR_ARG;
+    std::vector<Task> ht(nregions);
+    int64_t off = 0;
+    for (size_t i = 0; i < nregions; i++) {
+        const lm_pa_region &r = regions[i];
+        const std::string at = "region " + std::to_string(i) + ": ";
+        auto refuse = [&](const std::string &m) {
+            ix->err = at + m;
+            return LM_ERR_ARG;
+        };
+        if (r.query >= nq) return refuse("query " + std::to_string(r.query) + " of " + std::to_string(nq));
+        if (r.qend > queries[r.query].len)
+            return refuse("qend " + std::to_string(r.qend) + " is past the query's " + std::to_string(queries[r.query].len) + " bases");
+        if (r.local_genome < 0 || r.local_genome >= (int64_t)ix->host.genomes.size())
+            return refuse("genome " + std::to_string(r.local_genome) + " is not a local genome of this handle (" +
+                          std::to_string(ix->host.genomes.size()) + ")");
+        const HostGenome &G = ix->host.genomes[(size_t)r.local_genome];
+        if (r.tbegin < 0) return refuse("tbegin " + std::to_string(r.tbegin) + " < 0");
+        if (r.wlen < 0) return refuse("wlen " + std::to_string(r.wlen) + " < 0");
+        if ((int64_t)r.tbegin + r.wlen > G.len)
+            return refuse("the window [" + std::to_string(r.tbegin) + ", +" + std::to_string(r.wlen) + ") ends past the genome's last base (" +
+                          std::to_string(G.len) + " bases)");
+        Task t;
+        memset(&t, 0, sizeof t);
+        t.seg = (uint32_t)i;
+        t.q = r.query;
+        t.g = (int32_t)r.local_genome;
+        t.bg = G.bg;
+        t.rc = r.rc ? 1 : 0;
+        t.tBegin = r.tbegin;
+        t.tEnd = r.tbegin + r.wlen - 1;
+        t.qBegin = (int32_t)r.qbegin;
+        t.qEnd = (int32_t)r.qend;
+        t.wlen = r.wlen;
+        t.woff = off; // (no window buffer behind it: the offsets only size the chunk, as in a search)
+        off += t.wlen;
+        ht[i] = t;
+    }
+    return pseudoalign_stage(ix, queries, nq, ht, true, std::vector<uint8_t>(), out, res_off, resv, anchor_off, anchors);
 }
 
 lm_status lm_wfa_batch(lm_index *ix, const lm_query *q, const lm_query *t, size_t n, lm_stage **out, const lm_wfa **resv,

@@ -38,6 +38,9 @@ void ha_pa_filter_build(const uint64_t *keys, int n, int K, int log, uint32_t *b
     for (int i = 0; i < n; i++) lm_pa_filter_set(keys[i], K, log, [&](uint64_t w, uint32_t m) { bits[w] |= m; });
 }
 uint64_t ha_pa_bits_words(int log) { return lm_pa_bits_words(log); }
+int ha_pa_filter_log(int64_t nk) { return lm_pa_filter_log(nk); } // what the query upload calls
+int ha_cmp_tab_bits(int64_t nk) { return lm_cmp_tab_bits(nk); }
+int ha_lcp(uint64_t a, uint64_t b, int K) { return lm_lcp(a, b, K); }
 int ha_pa_candidate2(const uint32_t *bits, int log, uint64_t key, int p, int K) {
     return lm_pa_candidate2(bits + lm_pa_bloom_word0(log), lm_pa_bloom_log(log), bits + lm_pa_map9_word0(log), bits, log,
                             (uint32_t)(key >> ((K - p) << 1)), p);

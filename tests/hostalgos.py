@@ -67,6 +67,9 @@ def lib():
         L.ha_pa_filter_build.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32)]
         L.ha_pa_candidate.argtypes = [C.POINTER(C.c_uint32), C.c_int, C.c_uint64, C.c_int, C.c_int]
         L.ha_pa_candidate2.argtypes = [C.POINTER(C.c_uint32), C.c_int, C.c_uint64, C.c_int, C.c_int]
+        L.ha_pa_filter_log.argtypes = [C.c_int64]
+        L.ha_cmp_tab_bits.argtypes = [C.c_int64]
+        L.ha_lcp.argtypes = [C.c_uint64, C.c_uint64, C.c_int]
         L.ha_pa_bits_words.argtypes = [C.c_int]
         L.ha_pa_bits_words.restype = C.c_uint64
         L.ha_bits_get.restype = C.c_uint64
