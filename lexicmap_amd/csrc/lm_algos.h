@@ -1298,7 +1298,9 @@ LM_HDN bool lm_tree_search_range(const uint64_t *keys, int n, uint64_t key, int 
 //   [W, 2W)       hashed bitmap of the 9-base prefixes, 2^log bits            (generic path only: lm_pa_candidate)
 //   [2W, 2W + B)  Bloom filter of the 11-base prefixes, two hash functions, 2^blog bits, blog = min(log, 19), B = 2^(blog-5)
 //   [.., + 8192)  exact bitmap of the 9-base prefixes (4^9 = 2^18 bits)
-// The last two (<= 96 KB) are what a workgroup of k_pa_filter keeps in LDS for the query it works on: a chain window of
+//   [.., + 8192)  rule map (2^18 bits): the partial-prefix rule below, settled per 9-base prefix (lm_pa_candidate3)
+// The Bloom filter and ONE of the last two (<= 96 KB) are what a workgroup of k_pa_filter keeps in LDS for the query it
+// works on (the rule map; the 9-base map with lm_tune::pa_rule_map off): a chain window of
 // an unrelated genome (most windows of a search against 10^5 genomes: random 17-base seed matches) is then rejected
 // position by position without a single global load; the 11-base bitmap in global memory is only asked for positions the
 // Bloom filter lets through when it is the more selective one (log > blog: reads above ~16 kb).
@@ -1311,6 +1313,14 @@ LM_HDN bool lm_tree_search_range(const uint64_t *keys, int n, uint64_t key, int 
 //     a >= p - 7 (bases [7, p) all A: rare, always a candidate) or d >= 8, so L >= 9 and the 9-base map must hit.
 //     lm_pa_candidate2 is sharper for the commonest case a = p - 9 (base 8 is not A, 3 in 4): then d = 9 and L = 10
 //     exactly, so one of the three 11-base prefixes that differ from the key's in base 10 (an A) must be present.
+// The rule map: for a key whose bases [9, p) are all A, every term of that rule is a function of the query and of the key's
+// first nine bases p9 alone - bases [7, p) all A <=> (p9 & 0xf) == 0; the 9-base map at p9; base 8 = p9 & 3; the three
+// siblings = (p9 << 4) | sib (bases 9 and 10 are A) - whatever p is.  Bit p9 of the map is set when
+//   * bases 7 and 8 of p9 are A (lm_pa_filter_preset: no k-mer needed), or
+//   * some k-mer has the 9-base prefix p9 and base 8 of p9 is A, or
+//   * some k-mer has the 11-base prefix (p9 << 4) | sib, sib in {1, 2, 3}
+// - the rule with exact set membership where lm_pa_candidate2 asks the Bloom filter and the hashed bitmap, so it passes no
+// key that lm_pa_candidate2 turns away, and it is still necessary.  lm_pa_candidate3 is then one bit test.
 #define LM_PFX_BASES 11
 #define LM_PFX_BASES2 9
 #define LM_PA_BLOOM_LOG_MAX 19
@@ -1332,7 +1342,7 @@ LM_HD uint32_t lm_pa_bloom_slot(uint32_t pfx, int which, int blog) {
     return lm_mul24(pfx, which ? 0xB2AE35u : 0xEBCA6Bu) >> (32 - blog);
 }
 LM_HD uint64_t lm_pa_bits_words(int log) {
-    return 2 * ((uint64_t)1 << (log - 5)) + ((uint64_t)1 << (lm_pa_bloom_log(log) - 5)) + ((uint64_t)1 << (LM_PA_MAP9_LOG - 5));
+    return 2 * ((uint64_t)1 << (log - 5)) + ((uint64_t)1 << (lm_pa_bloom_log(log) - 5)) + 2 * ((uint64_t)1 << (LM_PA_MAP9_LOG - 5));
 }
 // the size class of a query's filter, as the query upload sizes it: ~16 bits per entry of the comparison index (nk = both strands
 // of every k-mer position of the query, kept or not), 2^13 .. 2^24 bits
@@ -1351,6 +1361,12 @@ LM_HD int lm_cmp_tab_bits(int64_t nk) {
 }
 LM_HD uint64_t lm_pa_bloom_word0(int log) { return 2 * ((uint64_t)1 << (log - 5)); }
 LM_HD uint64_t lm_pa_map9_word0(int log) { return lm_pa_bloom_word0(log) + ((uint64_t)1 << (lm_pa_bloom_log(log) - 5)); }
+LM_HD uint64_t lm_pa_rule_word0(int log) { return lm_pa_map9_word0(log) + ((uint64_t)1 << (LM_PA_MAP9_LOG - 5)); }
+// the bits of the rule map no k-mer is needed for (bases 7 and 8 of p9 are A: bits 0 and 16 of every word), words
+// j0, j0 + step, ... of the map: set once per query beside lm_pa_filter_set, so that the test per position stays one bit
+template <typename OrBit> LM_HD void lm_pa_filter_preset(int log, int j0, int step, OrBit or_bit) {
+    for (int j = j0; j < (1 << (LM_PA_MAP9_LOG - 5)); j += step) or_bit(lm_pa_rule_word0(log) + (uint64_t)j, 0x00010001u);
+}
 // every bit a k-mer of the query sets (`or_bit(word index, mask)`: atomicOr on the device)
 template <typename OrBit> LM_HD void lm_pa_filter_set(uint64_t key, int K, int log, OrBit or_bit) {
     const uint32_t p11 = (uint32_t)(key >> ((K - LM_PFX_BASES) << 1)), p9 = (uint32_t)(key >> ((K - LM_PFX_BASES2) << 1));
@@ -1362,6 +1378,9 @@ template <typename OrBit> LM_HD void lm_pa_filter_set(uint64_t key, int K, int l
     or_bit(lm_pa_bloom_word0(log) + (a >> 5), 1u << (a & 31));
     or_bit(lm_pa_bloom_word0(log) + (b >> 5), 1u << (b & 31));
     or_bit(lm_pa_map9_word0(log) + (p9 >> 5), 1u << (p9 & 31));
+    // the rule map at the k-mer's own 9-base prefix: as a k-mer that shares nine bases with a key whose base 8 is an A, or
+    // as a sibling (bases 9 and 10 = A, then not A) of a key with that prefix
+    if ((p9 & 3u) == 0 || ((p11 & 0xfu) >= 1u && (p11 & 0xfu) <= 3u)) or_bit(lm_pa_rule_word0(log) + (p9 >> 5), 1u << (p9 & 31));
 }
 LM_HD bool lm_pa_candidate(const uint32_t *bits, int log, uint64_t key, int p, int K) {
     const uint32_t h = lm_pa_filter_slot((uint32_t)(key >> ((K - LM_PFX_BASES) << 1)), log);
@@ -1406,6 +1425,24 @@ LM_HD bool lm_pa_candidate2(const uint32_t *bloom, int blog, const uint32_t *map
         return false;
     }
     return true; // base 8 is an A: the 9-base map was the test
+}
+// the same test with the partial-prefix rule read from the query's rule map (`rule`: the LDS copy on the device): the 11-base
+// tests hit, or the bases [9, p) are all A and the rule map has the bit of the key's first nine bases.  Sharper than
+// lm_pa_candidate2 (exact membership in the rule) and still necessary; what k_pa_filter computes per (position, strand).
+LM_HD bool lm_pa_rule_bit(const uint32_t *rule, uint32_t f, int p) {
+    const uint32_t p9 = f >> ((p - LM_PFX_BASES2) << 1);
+    return (f & ((1u << ((p - 9) << 1)) - 1u)) == 0 && ((rule[p9 >> 5] >> (p9 & 31)) & 1u) != 0;
+}
+LM_HD bool lm_pa_candidate3(const uint32_t *bloom, int blog, const uint32_t *rule, const uint32_t *bits11, int log,
+                            uint32_t f, int p) {
+    const uint32_t p11 = f >> ((p - LM_PFX_BASES) << 1);
+    const uint32_t a = lm_pa_bloom_slot(p11, 0, blog), b = lm_pa_bloom_slot(p11, 1, blog);
+    bool hit = (((bloom[a >> 5] >> (a & 31)) & (bloom[b >> 5] >> (b & 31))) & 1u) != 0;
+    if (hit && log > blog) {
+        const uint32_t h = lm_pa_filter_slot(p11, log);
+        hit = ((bits11[h >> 5] >> (h & 31)) & 1u) != 0;
+    }
+    return hit || lm_pa_rule_bit(rule, f, p);
 }
 
 // Same, with the two binary searches narrowed by a bucket table over the leading `tab_bits/2` bases:

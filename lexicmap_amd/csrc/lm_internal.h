@@ -478,6 +478,7 @@ struct lm_tune {
     int pa_filter_roll = 1;  // k_pa_filter: a lane takes consecutive window positions (immediate funnel shifts over its own 64-base string); LM_PA_FILTER_ROLL=0: every 64th position, words passed between lanes
     int pa_seg_by_group = 1; // candidate segments by task group + XCD-local k_pa_search
     int pa_drop_nested = 1;  // k_pa_search does not emit anchors nested in their neighbour's, which ClearSubstrPairs would drop (lm_pa_anchor_nested); LM_PA_DROP_NESTED=0: every anchor
+    int pa_rule_map = 1;     // k_pa_filter settles the partial-prefix rule with one bit of the query's rule map (lm_pa_candidate3) and queues only Bloom hits of long reads; LM_PA_RULE_MAP=0: 9-base map in LDS, pa_partial_rule, every lane with bases [9, p) all A queued (lm_pa_candidate2)
     int wfa_resident_pct = 100; // share of the CUs' wavefront slots / LDS the persistent WFA kernels take (75 / 50 % measured in round 3: no gain / -20 %)
     int arena_reserve_pct = 90; // LM_ARENA_RESERVE_PCT: share of the scratch budget cut into the two lane slabs when a production-size index is opened, else at the first search (LaneSlabs; 0: slabs on demand as in round 4)
     int two_lanes = 1;       // two parts of a batch searched side by side, each with half of the scratch budget (LM_TWO_LANES=0: one after the other)
@@ -501,6 +502,7 @@ struct lm_tune {
         if (const char *e = getenv("LM_ARENA_RESERVE_PCT")) arena_reserve_pct = std::max(0, std::min(100, atoi(e)));
         if (const char *e = getenv("LM_PA_FILTER_ROLL")) pa_filter_roll = atoi(e) != 0;
         if (const char *e = getenv("LM_PA_DROP_NESTED")) pa_drop_nested = atoi(e) != 0;
+        if (const char *e = getenv("LM_PA_RULE_MAP")) pa_rule_map = atoi(e) != 0;
     }
 };
 

@@ -136,7 +136,8 @@ __global__ void k_build_cmp_tab(const uint64_t *__restrict__ keys_cmp, const int
 // hashed bitmaps of 2^log bits over the 11-base prefixes (the smallest prefix length SeqComparator.Compare ever asks for,
 // lib-seq_compare.go:339-348) and the 9-base prefixes of its (filtered) k-mers, sized per query with ~16 bits per k-mer
 // (a 1.5-kb gene: 64 Kbit, a 50-kb read: 2 Mbit), plus the two maps k_pa_filter keeps in LDS: a two-hash Bloom filter
-// of the 11-base prefixes (<= 2^19 bits) and the exact 2^18-bit map of the 9-base prefixes.
+// of the 11-base prefixes (<= 2^19 bits) and the 2^18-bit rule map of the partial-prefix rule (or, with the rule map switched
+// off, the exact 2^18-bit map of the 9-base prefixes).
 __global__ __launch_bounds__(256) void k_build_cmp_bits(const uint64_t *__restrict__ keys_cmp,
                                                          const int64_t *__restrict__ posoff,
                                                          const int32_t *__restrict__ nvalid, int nq, int K,
@@ -148,6 +149,7 @@ __global__ __launch_bounds__(256) void k_build_cmp_bits(const uint64_t *__restri
         const int n = nvalid[q];
         const int log = bits_log[q];
         uint32_t *b = bits + bits_off[q];
+        lm_pa_filter_preset(log, (int)threadIdx.x, (int)blockDim.x, [&](uint64_t w, uint32_t m) { atomicOr(&b[w], m); });
         for (int j = threadIdx.x; j < n; j += blockDim.x)
             lm_pa_filter_set(keys[j], K, log, [&](uint64_t w, uint32_t m) { atomicOr(&b[w], m); });
     }
@@ -1037,8 +1039,9 @@ __device__ __forceinline__ void pa_prefixes(const Task &t, const uint8_t *__rest
 // Two kernels replace a count / scan / emit triple over the window positions.
 //
 // k_pa_filter: a workgroup of 1024 threads takes PA_GROUP consecutive chain windows (tasks are in (query, genome) order, so
-// nearly always windows of ONE query) and keeps that query's Bloom filter of 11-base k-mer prefixes and its exact 9-base
-// prefix map in LDS (96 KB, lm_pa_candidate2).  Per window position a lane extracts the first p bases of the k-mer and of
+// nearly always windows of ONE query) and keeps that query's Bloom filter of 11-base k-mer prefixes and its rule map (the
+// partial-prefix rule of tree.Search settled per 9-base prefix when the filters are built) in LDS (96 KB, lm_pa_candidate3).
+// Per window position a lane extracts the first p bases of the k-mer and of
 // its reverse complement from the 2-bit genome and asks the LDS maps: at 10^5 genomes nine windows in ten belong to
 // unrelated genomes (random 17-base seed matches) and ~97 % of their positions end there, without a global load beyond the
 // (coalesced) genome words.  What the Bloom filter lets through asks the query's 11-base bitmap in global memory when that
@@ -1062,13 +1065,16 @@ static_assert(PA_WAVES == LM_PA_RANGE_SEGS, "one candidate segment per wavefront
 // ROLL (K == 31): a lane takes ceil(np / 64) CONSECUTIVE positions of a slice instead of every 64th, so the 32-bit windows
 // that hold the first p bases of a k-mer and of its reverse complement are funnel shifts by IMMEDIATES over the lane's own
 // 64-base string (and its reverse complement, built once per slice) - no cross-lane traffic, no 64-bit shifts, no per-position
-// reverse complement: ~50 vector instructions per position pair where the strided form (ROLL = false, kept for K != 31) has ~100.
+// reverse complement.  Measured at C3 (SQ_INSTS_VALU per 64 window positions, both strands, everything the kernel does
+// included): 108 vector, 55 scalar and 12 LDS instructions with the rule map, 126 / 71 / 13 without it (profiles/README.md);
+// the strided form (ROLL = false, kept for K != 31) has about twice the vector work.
 #define PA_SLICE_ROLL 2048 /* 64 lanes x 32 positions */
 // reverse complement of the 16 bases of a dword (first base in the top bits)
 __device__ __forceinline__ uint32_t pa_rc16(uint32_t x) {
     const uint32_t y = __builtin_bitreverse32(~x);
     return ((y >> 1) & 0x55555555u) | ((y & 0x55555555u) << 1);
 }
+// Only with the rule map switched off (RULE = false, lm_tune::pa_rule_map): the rule evaluated per position.
 // lm_pa_candidate2 for the lanes `q` of a wavefront whose key f (first p bases) FAILED its own Bloom test, has bases [9, p) all
 // A and belongs to a query without a global 11-base bitmap (log <= blog); the other lanes keep `c`.  One lane in eight is such
 // a lane, so EVERY pass of a wavefront comes here, and the literal rule - three sibling prefixes, two hashes and two LDS reads
@@ -1097,7 +1103,10 @@ __device__ __forceinline__ bool pa_partial_rule(bool q, bool c, uint32_t f, int 
 // SRC: the tasks read their 2-bit bases through per-task sources (TaskSrc: a handle with host-resident genomes).  SRC = false is
 // the kernel of a handle with every genome in the device store: ix.gbits + g_off[g], the code it always was (the source
 // array costs that instantiation nothing - no argument is read, no register held, no LDS).
-template <bool ROLL, bool SRC>
+// RULE: the partial-prefix rule is one bit of the query's rule map (lm_pa_candidate3; the map takes the 32 KB of LDS of the
+// 9-base map) and only Bloom hits of a long read wait for the global bitmap.  RULE = false (lm_tune::pa_rule_map off) is the
+// kernel as it was: 9-base map in LDS, pa_partial_rule, every lane with bases [9, p) all A of a long read in the pending list.
+template <bool ROLL, bool SRC, bool RULE>
 __global__ __launch_bounds__(PA_THREADS) void k_pa_filter(DevIndexView ix, const Task *__restrict__ tasks,
                                                            const TaskSrc *__restrict__ src, int64_t ntasks,
                                                            const uint8_t *__restrict__ wbuf,
@@ -1119,7 +1128,7 @@ __global__ __launch_bounds__(PA_THREADS) void k_pa_filter(DevIndexView ix, const
     extern __shared__ uint64_t pa_lds[];                               // PA_LDS_BYTES, dynamic (above 64 KB)
     uint64_t *s_stage = pa_lds;                                        // [PA_WAVES][PA_STAGE]
     uint32_t *s_bloom = (uint32_t *)(pa_lds + PA_WAVES * PA_STAGE);    // 64 KB
-    uint32_t *s_map9 = s_bloom + (1 << (LM_PA_BLOOM_LOG_MAX - 5));     // 32 KB
+    uint32_t *s_map9 = s_bloom + (1 << (LM_PA_BLOOM_LOG_MAX - 5));     // 32 KB: the rule map (RULE) or the 9-base map
     uint64_t *s_pend_rec = (uint64_t *)(s_map9 + (1 << (LM_PA_MAP9_LOG - 5))); // [PA_WAVES][PA_PEND]
     uint32_t *s_pend_pf = (uint32_t *)(s_pend_rec + PA_WAVES * PA_PEND);        // [PA_WAVES][PA_PEND]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1159,7 +1168,13 @@ __global__ __launch_bounds__(PA_THREADS) void k_pa_filter(DevIndexView ix, const
         if (lane < cnt) {
             const uint32_t e = pend_pf[idx];
             rec = pend_rec[idx];
-            c = lm_pa_candidate2(s_bloom, cur_blog, s_map9, cur_qbits, cur_log, e & 0x3fffffffu, LM_PFX_BASES + 2 * (int)(e >> 30));
+            if constexpr (RULE) {
+                // a Bloom hit that did not pass the rule map (pend2): the hashed bitmap is all that is left of lm_pa_candidate3
+                const uint32_t h = lm_pa_filter_slot((e & 0x3fffffffu) >> (4 * (int)(e >> 30)), cur_log);
+                c = ((cur_qbits[h >> 5] >> (h & 31)) & 1u) != 0;
+            } else {
+                c = lm_pa_candidate2(s_bloom, cur_blog, s_map9, cur_qbits, cur_log, e & 0x3fffffffu, LM_PFX_BASES + 2 * (int)(e >> 30));
+            }
         }
         n_pend -= cnt;
         push(c, rec);
@@ -1173,6 +1188,24 @@ __global__ __launch_bounds__(PA_THREADS) void k_pa_filter(DevIndexView ix, const
             pend_rec[slot] = rec;
         }
         n_pend += __popcll(m);
+        while (n_pend >= 64) pend_round(64);
+    };
+    auto pend2 = [&](bool a0, bool a1, uint32_t e0, uint32_t e1, uint64_t rec) { // both strands of a position with one reservation
+        const uint64_t m0 = __ballot(a0), m1 = __ballot(a1);
+        if ((m0 | m1) == 0ull) return;
+        const int n0 = __popcll(m0), n1 = __popcll(m1);
+        if (n_pend + n0 + n1 > PA_PEND) pend_round(n_pend); // (n_pend < 64 on entry: the two strands alone always fit)
+        if (a0) {
+            const int slot = n_pend + __popcll(m0 & lt_mask);
+            pend_pf[slot] = e0;
+            pend_rec[slot] = rec;
+        }
+        if (a1) {
+            const int slot = n_pend + n0 + __popcll(m1 & lt_mask);
+            pend_pf[slot] = e1;
+            pend_rec[slot] = rec | 1ull;
+        }
+        n_pend += n0 + n1;
         while (n_pend >= 64) pend_round(64);
     };
     // per group: the tasks' fields every wavefront needs (one round of dependent global loads for the whole group instead
@@ -1235,7 +1268,7 @@ __global__ __launch_bounds__(PA_THREADS) void k_pa_filter(DevIndexView ix, const
             cur_blog = blog;
             // this query's LDS maps (K >= 16 and a query with maps: the fast path exists for some window of it)
             if (qbits != nullptr && K >= 16) {
-                const uint32_t *gbl = qbits + lm_pa_bloom_word0(log), *g9 = qbits + lm_pa_map9_word0(log);
+                const uint32_t *gbl = qbits + lm_pa_bloom_word0(log), *g9 = qbits + (RULE ? lm_pa_rule_word0(log) : lm_pa_map9_word0(log));
                 const int nb = 1 << (blog - 5);
                 for (int j = tid; j < nb; j += PA_THREADS) s_bloom[j] = gbl[j];
                 for (int j = tid; j < (1 << (LM_PA_MAP9_LOG - 5)); j += PA_THREADS) s_map9[j] = g9[j];
@@ -1335,17 +1368,31 @@ __global__ __launch_bounds__(PA_THREADS) void k_pa_filter(DevIndexView ix, const
                             const uint32_t b10 = s_bloom[s10 >> 5], b11 = s_bloom[s11 >> 5];
                             const bool h0 = in && (((b00 >> (s00 & 31)) & (b01 >> (s01 & 31))) & 1u) != 0;
                             const bool h1 = in && (((b10 >> (s10 & 31)) & (b11 >> (s11 & 31))) & 1u) != 0;
-                            const bool q0 = in && !h0 && (pf0 & m9p) == 0, q1 = in && !h1 && (pf1 & m9p) == 0;
-                            c0 = h0;
-                            c1 = h1;
-                            if (log > blog) { // long reads: the global 11-base bitmap, 64 pending positions at a time (see below)
-                                c0 = c1 = false;
-                                const uint64_t rec = rec_t | ((uint64_t)(uint32_t)i << 1);
-                                pend(h0 || q0, pf0 | pcode, rec);
-                                pend(h1 || q1, pf1 | pcode, rec | 1ull);
-                            } else if (__ballot(q0 || q1) != 0ull) { // the partial-prefix rule, all in LDS here (rare lanes)
-                                c0 = pa_partial_rule(q0, c0, pf0, p, blog, s_bloom, s_map9); // (lm_pa_candidate2 for these lanes, in LDS)
-                                c1 = pa_partial_rule(q1, c1, pf1, p, blog, s_bloom, s_map9);
+                            if constexpr (RULE) {
+                                // lm_pa_candidate3: the rule map settles the partial-prefix rule for every lane, with one LDS
+                                // read and no branch; of a long read only the Bloom hits it does not pass wait for the global
+                                // 11-base bitmap, 64 pending positions at a time (see below)
+                                const bool r0 = in && lm_pa_rule_bit(s_map9, pf0, p), r1 = in && lm_pa_rule_bit(s_map9, pf1, p);
+                                c0 = h0 || r0;
+                                c1 = h1 || r1;
+                                if (log > blog) {
+                                    c0 = r0;
+                                    c1 = r1;
+                                    pend2(h0 && !r0, h1 && !r1, pf0 | pcode, pf1 | pcode, rec_t | ((uint64_t)(uint32_t)i << 1));
+                                }
+                            } else {
+                                const bool q0 = in && !h0 && (pf0 & m9p) == 0, q1 = in && !h1 && (pf1 & m9p) == 0;
+                                c0 = h0;
+                                c1 = h1;
+                                if (log > blog) { // long reads: the global 11-base bitmap, 64 pending positions at a time (see below)
+                                    c0 = c1 = false;
+                                    const uint64_t rec = rec_t | ((uint64_t)(uint32_t)i << 1);
+                                    pend(h0 || q0, pf0 | pcode, rec);
+                                    pend(h1 || q1, pf1 | pcode, rec | 1ull);
+                                } else if (__ballot(q0 || q1) != 0ull) { // the partial-prefix rule, all in LDS here (rare lanes)
+                                    c0 = pa_partial_rule(q0, c0, pf0, p, blog, s_bloom, s_map9); // (lm_pa_candidate2 for these lanes, in LDS)
+                                    c1 = pa_partial_rule(q1, c1, pf1, p, blog, s_bloom, s_map9);
+                                }
                             }
                             const uint64_t m0 = __ballot(c0), m1 = __ballot(c1);
                             if ((m0 | m1) != 0ull) {
@@ -1387,9 +1434,9 @@ __global__ __launch_bounds__(PA_THREADS) void k_pa_filter(DevIndexView ix, const
                         const uint32_t pf0 = t.rc ? rl : first, pf1 = t.rc ? first : rl;
                         const int i = t.rc ? p1 - 1 - r : p0 + r; // window position
                         const bool in = r < np;
-                        // lm_pa_candidate2 for both strands with the common case free of branches: two Bloom bits per
-                        // strand from LDS; the global 11-base bitmap (long reads) and the partial-prefix rule (bases [9, p)
-                        // all A: one k-mer in 16) are left to the few lanes that need them
+                        // the test for both strands with the common case free of branches: two Bloom bits per strand from
+                        // LDS, then (RULE) one bit of the rule map, or (RULE = false) the partial-prefix rule for the few lanes
+                        // with bases [9, p) all A; the global 11-base bitmap (long reads) is left to the pending list
                         bool c0, c1;
                         {
                             const uint32_t a0 = pf0 >> ((p - LM_PFX_BASES) << 1), a1 = pf1 >> ((p - LM_PFX_BASES) << 1);
@@ -1399,24 +1446,36 @@ __global__ __launch_bounds__(PA_THREADS) void k_pa_filter(DevIndexView ix, const
                             const uint32_t b10 = s_bloom[s10 >> 5], b11 = s_bloom[s11 >> 5];
                             const bool h0 = in && (((b00 >> (s00 & 31)) & (b01 >> (s01 & 31))) & 1u) != 0;
                             const bool h1 = in && (((b10 >> (s10 & 31)) & (b11 >> (s11 & 31))) & 1u) != 0;
-                            const uint32_t m9p = (1u << ((p - 9) << 1)) - 1u;
-                            const bool q0 = in && !h0 && (pf0 & m9p) == 0, q1 = in && !h1 && (pf1 & m9p) == 0;
-                            c0 = h0;
-                            c1 = h1;
-                            if (log > blog) {
-                                // long reads: what the Bloom filter lets through must ask the 11-base bitmap in global
-                                // memory.  Asked where it arises, nearly every pass of the loop would stall on that load
-                                // for the sake of a handful of lanes; the lanes concerned are set aside in the wavefront's
-                                // pending list instead and examined 64 at a time (one load for 64 useful lanes)
-                                c0 = c1 = false;
-                                const uint64_t rec = rec_t | ((uint64_t)(uint32_t)i << 1);
+                            if constexpr (RULE) { // (as in the rolling branch: lm_pa_candidate3)
+                                const bool r0 = in && lm_pa_rule_bit(s_map9, pf0, p), r1 = in && lm_pa_rule_bit(s_map9, pf1, p);
                                 const uint32_t pcode = (uint32_t)((p - LM_PFX_BASES) >> 1) << 30; // p = 11, 13 or 15
-                                pend(h0 || q0, pf0 | pcode, rec);
-                                pend(h1 || q1, pf1 | pcode, rec | 1ull);
-                            } else if (__ballot(q0 || q1) != 0ull) {
-                                // the partial-prefix rule, all in LDS here (rare lanes)
-                                c0 = pa_partial_rule(q0, c0, pf0, p, blog, s_bloom, s_map9); // (lm_pa_candidate2 for these lanes, in LDS)
-                                c1 = pa_partial_rule(q1, c1, pf1, p, blog, s_bloom, s_map9);
+                                c0 = h0 || r0;
+                                c1 = h1 || r1;
+                                if (log > blog) {
+                                    c0 = r0;
+                                    c1 = r1;
+                                    pend2(h0 && !r0, h1 && !r1, pf0 | pcode, pf1 | pcode, rec_t | ((uint64_t)(uint32_t)i << 1));
+                                }
+                            } else {
+                                const uint32_t m9p = (1u << ((p - 9) << 1)) - 1u;
+                                const bool q0 = in && !h0 && (pf0 & m9p) == 0, q1 = in && !h1 && (pf1 & m9p) == 0;
+                                c0 = h0;
+                                c1 = h1;
+                                if (log > blog) {
+                                    // long reads: what the Bloom filter lets through must ask the 11-base bitmap in global
+                                    // memory.  Asked where it arises, nearly every pass of the loop would stall on that load
+                                    // for the sake of a handful of lanes; the lanes concerned are set aside in the wavefront's
+                                    // pending list instead and examined 64 at a time (one load for 64 useful lanes)
+                                    c0 = c1 = false;
+                                    const uint64_t rec = rec_t | ((uint64_t)(uint32_t)i << 1);
+                                    const uint32_t pcode = (uint32_t)((p - LM_PFX_BASES) >> 1) << 30; // p = 11, 13 or 15
+                                    pend(h0 || q0, pf0 | pcode, rec);
+                                    pend(h1 || q1, pf1 | pcode, rec | 1ull);
+                                } else if (__ballot(q0 || q1) != 0ull) {
+                                    // the partial-prefix rule, all in LDS here (rare lanes)
+                                    c0 = pa_partial_rule(q0, c0, pf0, p, blog, s_bloom, s_map9); // (lm_pa_candidate2 for these lanes, in LDS)
+                                    c1 = pa_partial_rule(q1, c1, pf1, p, blog, s_bloom, s_map9);
+                                }
                             }
                         }
                         // both strands appended with one reservation in the wavefront's strip
@@ -2704,25 +2763,26 @@ void launch_build_cmp_bits(hipStream_t st, const uint64_t *keys_cmp, const int64
     int g = nq < 1 ? 1 : (nq > 65536 ? 65536 : nq);
     hipLaunchKernelGGL(k_build_cmp_bits, dim3(g), dim3(256), 0, st, keys_cmp, posoff, nvalid, nq, K, bits_off, bits_log, bits);
 }
+static decltype(&k_pa_filter<true, true, true>) pa_filter_kernel(bool roll, bool src, bool rule) {
+    if (rule) return src ? (roll ? k_pa_filter<true, true, true> : k_pa_filter<false, true, true>) : (roll ? k_pa_filter<true, false, true> : k_pa_filter<false, false, true>);
+    return src ? (roll ? k_pa_filter<true, true, false> : k_pa_filter<false, true, false>) : (roll ? k_pa_filter<true, false, false> : k_pa_filter<false, false, false>);
+}
 void launch_pa_filter(hipStream_t st, DevIndexView ix, const Task *tasks, const TaskSrc *src, int64_t ntasks, const uint8_t *wbuf,
                       const int64_t *posoff, const int32_t *nvalid, const uint32_t *cmp_bits, const int64_t *bits_off,
                       const int32_t *bits_log, int K, int min_prefix, unsigned long long *seg_count, int nseg, int64_t seg_cap,
-                      uint64_t *cand, unsigned long long *group_counter, int ncu, int seg_by_group, bool roll) {
+                      uint64_t *cand, unsigned long long *group_counter, int ncu, int seg_by_group, bool roll, bool rule) {
     const int64_t ngroups = (ntasks + PA_GROUP - 1) / PA_GROUP;
     int g = (int)(ngroups < 1 ? 1 : (ngroups > ncu ? ncu : ngroups));
     static bool lds_set = false;
     if (!lds_set) {
-        (void)hipFuncSetAttribute((const void *)k_pa_filter<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, PA_LDS_BYTES);
-        (void)hipFuncSetAttribute((const void *)k_pa_filter<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, PA_LDS_BYTES);
-        (void)hipFuncSetAttribute((const void *)k_pa_filter<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PA_LDS_BYTES);
-        (void)hipFuncSetAttribute((const void *)k_pa_filter<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PA_LDS_BYTES);
+        for (int v = 0; v < 8; v++) (void)hipFuncSetAttribute((const void *)pa_filter_kernel(v & 1, v & 2, v & 4), hipFuncAttributeMaxDynamicSharedMemorySize, PA_LDS_BYTES);
         lds_set = true;
     }
     // ROLL slices a window into pieces of up to PA_SLICE_ROLL = 2048 positions and takes its rolling branch only for K == 31; any
     // other k would fall into the strided branch, whose one-load-per-lane word cache covers 64 x 32 bases = PA_SLICE positions only
     // (the end of a 2048-position slice came out garbled and candidates were dropped): other k run the strided instantiation
     roll = roll && K == 31;
-    auto kern = src ? (roll ? k_pa_filter<true, true> : k_pa_filter<false, true>) : (roll ? k_pa_filter<true, false> : k_pa_filter<false, false>);
+    auto kern = pa_filter_kernel(roll, src != nullptr, rule);
     hipLaunchKernelGGL(kern, dim3(g), dim3(PA_THREADS), PA_LDS_BYTES, st, ix, tasks, src, ntasks, wbuf,
                        posoff, nvalid, cmp_bits, bits_off, bits_log, K, min_prefix, seg_count, nseg, seg_cap, cand, group_counter,
                        seg_by_group);

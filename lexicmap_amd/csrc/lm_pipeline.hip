@@ -1602,7 +1602,8 @@ static lm_qbatch *upload_part(lm_index *ix, const lm_query *queries, size_t nq, 
         h2d(ix, qb->d_posoff, qb->h_posoff);
         h2d(ix, qb->d_segoff, segoff);
         {   // prefix filters of the pseudo-alignment (lm_pa_bits_words, lm_algos.h): ~16 bits per k-mer (both strands) in
-            // each hashed map, 2^13 .. 2^24 bits, + the Bloom filter and the exact 9-base map k_pa_filter keeps in LDS
+            // each hashed map, 2^13 .. 2^24 bits, + the Bloom filter, the exact 9-base map and the rule map (k_pa_filter keeps the
+            // Bloom filter and one of the two maps in LDS)
             std::vector<int64_t> boff(nq + 1, 0);
             std::vector<int32_t> blog(nq + 1, 13);
             for (size_t i = 0; i < nq; i++) {
@@ -1673,7 +1674,10 @@ extern "C" lm_status lm_qbatch_upload(lm_index *ix, const lm_query *queries, siz
                           std::to_string(max_pos) + " k-mers)";
                 return LM_ERR_ARG;
             }
-            if (nqp > 0 && (pos + np > max_pos || (nqp + 1) * (int64_t)M > max_qm)) {
+            // (a query's prefix filter has a part that does not depend on its length - the exact 9-base map and the rule map,
+            // 32 KB each, lm_pa_bits_words: counted with the other per-query arrays, as the (query, mask) pairs that take as much)
+            const int64_t per_q = (int64_t)M + (2 * ((int64_t)1 << (LM_PA_MAP9_LOG - 3)) + 79) / 80;
+            if (nqp > 0 && (pos + np > max_pos || (nqp + 1) * per_q > max_qm)) {
                 cuts.push_back(i);
                 pos = 0;
                 nqp = 0;
@@ -1994,7 +1998,8 @@ static void run_pseudo(AlignCtx &a, TaskSpan ht, std::vector<int64_t> &res_off_h
             Prof p(ix, "k_pa_filter", W);
             launch_pa_filter(S(ix), ix->view, tasks_d, src_d, nt, a.wb, qb->posoff_cmp(), a.w->nvalid.p, a.w->cmp_bits.p,
                              qb->d_bits_off.p, qb->d_bits_log.p, LM_CMP_K, 11, a.pa_count.p + 2, nseg, seg_cap, a.B1.p,
-                             a.pa_count.p + 1, device_cus(ix->device), by_group ? 1 : 0, ix->tune.pa_filter_roll != 0);
+                             a.pa_count.p + 1, device_cus(ix->device), by_group ? 1 : 0, ix->tune.pa_filter_roll != 0,
+                             ix->tune.pa_rule_map != 0);
         }
         {
             Prof p(ix, "k_pa_search");
