@@ -76,7 +76,27 @@ class Chain2(C.Structure):
                 ("aligned_bases_t", C.c_int32), ("pident", C.c_double)]
 
 
-LM_ERR_ARG = 7  # lm_status
+LM_ERR_OPTION, LM_ERR_ARG = 3, 7  # lm_status
+REFUSED_ARG = (LM_ERR_ARG,)                    # calls without an option check
+REFUSED_ARG_OR_OPTION = (LM_ERR_OPTION, LM_ERR_ARG)
+
+
+def _check(st, text, fmt="liblexicmap_hip error %(status)d: %(text)s", refused=()):
+    """The one place a status of the library becomes an exception; returns when st is 0.  text: the library's error text, or a
+    callable that fetches it (called only for a failure).  refused: the statuses by which this call refuses the caller's
+    argument or option - they raise ValueError with the bare text.  Every other status raises RuntimeError with
+    fmt % {"status": st, "text": text}.  The exception carries the status as e.status."""
+    if st == 0:
+        return
+    if callable(text):
+        text = text()
+    e = ValueError(text) if st in refused else RuntimeError(fmt % {"status": st, "text": text})
+    e.status = st
+    raise e
+
+
+def _global_error():
+    return lib().lm_last_error(None).decode()
 
 
 class PaRegion(C.Structure):
@@ -428,8 +448,7 @@ class Index:
             st = L.lm_index_open(path.encode(), C.byref(self.opt), device, C.byref(h))
         else:
             st = L.lm_index_open_ex(path.encode(), C.byref(self.opt), C.byref(residency), device, C.byref(h))
-        if st != 0:
-            raise RuntimeError("lm_index_open failed (%d): %s" % (st, L.lm_last_error(None).decode()))
+        _check(st, _global_error, "lm_index_open failed (%(status)d): %(text)s")
         self.h = h
 
     @classmethod
@@ -445,8 +464,7 @@ class Index:
             st = L.lm_index_build_synthetic(C.byref(sp), C.byref(opt), device, C.byref(h))
         else:
             st = L.lm_index_build_synthetic_ex(C.byref(sp), C.byref(opt), C.byref(residency), device, C.byref(h))
-        if st != 0:
-            raise RuntimeError("lm_index_build_synthetic failed (%d): %s" % (st, L.lm_last_error(None).decode()))
+        _check(st, _global_error, "lm_index_build_synthetic failed (%(status)d): %(text)s")
         return cls(None, opt, device, _handle=h)
 
     @classmethod
@@ -504,21 +522,18 @@ class Index:
         """lm_index_get_residency: genomes and 2-bit bytes on the device / in pinned host memory, staging bytes held"""
         r = ResidencyInfo()
         st = lib().lm_index_get_residency(self.h, C.byref(r))
-        if st != 0:
-            self._err(st)
+        self._err(st)
         return {f[0]: getattr(r, f[0]) for f in ResidencyInfo._fields_}
 
     def save(self, path, chunks=16):
         """the resident index written in the reference's on-disk format (lm_index_save)"""
         st = lib().lm_index_save(self.h, path.encode(), chunks)
-        if st != 0:
-            self._err(st)
+        self._err(st)
 
     def fetch(self, local_genome, start, length):
         buf = C.create_string_buffer(length)
         st = lib().lm_index_fetch(self.h, local_genome, start, length, buf)
-        if st != 0:
-            self._err(st)
+        self._err(st)
         return buf.raw
 
     def close(self):
@@ -526,8 +541,9 @@ class Index:
             lib().lm_index_close(self.h)
             self.h = None
 
-    def _err(self, st):
-        raise RuntimeError("liblexicmap_hip error %d: %s" % (st, lib().lm_last_error(self.h).decode()))
+    def _err(self, st, refused=()):
+        """raises for a status other than 0 of a call on this handle, with the handle's error text (_check)"""
+        _check(st, lambda: lib().lm_last_error(self.h).decode(), refused=refused)
 
     def info(self):
         i = IndexInfo()
@@ -546,14 +562,12 @@ class Index:
         import numpy as np
         n = C.c_size_t()
         st = lib().lm_index_mask_seeds(self.h, mask, None, None, 0, C.byref(n))
-        if st != 0:
-            self._err(st)
+        self._err(st)
         k = np.zeros(max(n.value, 1), dtype=np.uint64)
         v = np.zeros(max(n.value, 1), dtype=np.uint64)
         st = lib().lm_index_mask_seeds(self.h, mask, k.ctypes.data_as(C.POINTER(C.c_uint64)),
                                        v.ctypes.data_as(C.POINTER(C.c_uint64)), n.value, C.byref(n))
-        if st != 0:
-            self._err(st)
+        self._err(st)
         return k[:n.value], v[:n.value]
 
     @staticmethod
@@ -562,11 +576,6 @@ class Index:
             return None, 0
         ks = [int(k) for k in keys]
         return (C.c_uint64 * max(len(ks), 1))(*ks), len(ks)
-
-    def _seed_err(self, st):
-        if st == 7:
-            raise ValueError(lib().lm_last_error(self.h).decode())
-        self._err(st)
 
     def seed_positions(self, keys=None):
         """lm_index_seed_positions: per selected record (keys: record keys batch << 17 | index in any order; None: every
@@ -578,8 +587,7 @@ class Index:
         arr, n = self._record_keys(keys)
         sp = C.c_void_p()
         st = L.lm_index_seed_positions(self.h, arr, n, C.byref(sp))
-        if st != 0:
-            self._seed_err(st)
+        self._err(st, REFUSED_ARG)
         try:
             off, locs = C.POINTER(C.c_int64)(), C.POINTER(C.c_uint32)()
             nrec = L.lm_seedpos_get(sp, None, C.byref(off), C.byref(locs))
@@ -602,8 +610,7 @@ class Index:
         opt = SeedDistOpt(min_dist, bins, bin_width, 0)
         sd = C.c_void_p()
         st = L.lm_index_seed_distances(self.h, arr, n, C.byref(opt), C.byref(sd))
-        if st != 0:
-            self._seed_err(st)
+        self._err(st, REFUSED_ARG)
         try:
             def take(fn, ctype, dtype):
                 p = C.POINTER(ctype)()
@@ -640,10 +647,7 @@ class Index:
         opt = ScreenOpt(min_prefix, windows, top_n, 1 if details else 0)
         sc = C.c_void_p()
         st = L.lm_index_screen_genomes(self.h, qs, len(genomes), C.byref(opt), C.byref(sc))
-        if st in (3, 7):
-            raise ValueError(L.lm_last_error(self.h).decode())
-        if st != 0:
-            self._err(st)
+        self._err(st, REFUSED_ARG_OR_OPTION)
         try:
             rows_p, keys_p, pref_p = C.POINTER(ScreenRow)(), C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint8)()
             n = L.lm_screen_rows(sc, C.byref(rows_p))
@@ -689,10 +693,7 @@ class Index:
         opt = PairOpt(21, masks, 0.25)
         p, nb = C.c_void_p(), C.c_size_t()
         st = L.lm_index_pair_seeds(self.h, arr, n, C.byref(opt), C.byref(p), C.byref(nb))
-        if st in (3, 7):
-            raise ValueError(L.lm_last_error(self.h).decode())
-        if st != 0:
-            self._err(st)
+        self._err(st, REFUSED_ARG_OR_OPTION)
         try:
             return C.string_at(p, nb.value)
         finally:
@@ -718,10 +719,7 @@ class Index:
     def _pairs_result(self, st, pr, want_stats, arrays):
         import numpy as np
         L = lib()
-        if st in (3, 7):
-            raise ValueError(L.lm_last_error(self.h).decode())
-        if st != 0:
-            self._err(st)
+        self._err(st, REFUSED_ARG_OR_OPTION)
         try:
             rows_p = C.POINTER(PairRow)()
             nr = L.lm_pairs_rows(pr, C.byref(rows_p))
@@ -744,10 +742,7 @@ class Index:
             L.lm_pairs_free(pr)
 
     def _subseq_result(self, st, sp):
-        if st == 7:
-            raise ValueError(lib().lm_last_error(self.h).decode())
-        if st != 0:
-            self._err(st)
+        self._err(st, REFUSED_ARG)
         return Subseqs(sp)
 
     def subseq(self, regions, upstream=0, downstream=0, ignore_errors=False):
@@ -793,8 +788,7 @@ class Index:
         L = lib()
         p, n = C.c_void_p(), C.c_size_t()
         st = L.lm_index_screen_structure(self.h, C.byref(p), C.byref(n))
-        if st != 0:
-            self._err(st)
+        self._err(st)
         try:
             return C.string_at(p, n.value)
         finally:
@@ -804,17 +798,13 @@ class Index:
         """lm_index_screen_add_structure: another shard's screen_structure(); once every shard has every other shard's,
         screen() on a shard gives the unsharded index's rows for its records.  None: back to the handle's own lists."""
         st = lib().lm_index_screen_add_structure(self.h, blob, len(blob) if blob else 0)
-        if st == 7:
-            raise ValueError(lib().lm_last_error(self.h).decode())
-        if st != 0:
-            self._err(st)
+        self._err(st, REFUSED_ARG)
 
     def upload(self, seqs):
         arr, keep = _queries(seqs)
         qb = C.c_void_p()
         st = lib().lm_qbatch_upload(self.h, arr, len(seqs), C.byref(qb))
-        if st != 0:
-            self._err(st)
+        self._err(st)
         return qb
 
     def free_batch(self, qb):
@@ -824,8 +814,7 @@ class Index:
         L = lib()
         res = C.c_void_p()
         st = L.lm_search_resident(self.h, qb, C.byref(res))
-        if st != 0:
-            self._err(st)
+        self._err(st)
         out = self._collect(res, want_rows)
         L.lm_result_free(res)
         return out
@@ -837,8 +826,7 @@ class Index:
         L = lib()
         res = C.c_void_p()
         st = L.lm_search_resident(self.h, qb, C.byref(res))
-        if st != 0:
-            self._err(st)
+        self._err(st)
         return self._view(res)
 
     def search_resident_keep_np(self, qb, keep_query, keep_bg):
@@ -851,8 +839,7 @@ class Index:
         res = C.c_void_p()
         st = L.lm_search_resident_keep(self.h, qb, kq.ctypes.data_as(C.POINTER(C.c_uint32)),
                                        kg.ctypes.data_as(C.POINTER(C.c_uint64)), len(kq), C.byref(res))
-        if st != 0:
-            self._err(st)
+        self._err(st)
         return self._view(res)
 
     def _view(self, res):
@@ -878,8 +865,7 @@ class Index:
         keys = list(keys or [])
         arr = (C.c_uint64 * max(len(keys), 1))(*keys)
         st = lib().lm_index_set_genome_filter(self.h, arr, len(keys))
-        if st != 0:
-            self._err(st)
+        self._err(st)
 
     def search_scores(self, qb):
         """(query, batch_genome, score) numpy arrays: this shard's candidates for the -n cut"""
@@ -888,8 +874,7 @@ class Index:
         sg, n = C.c_void_p(), C.c_size_t()
         q, g, s = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint64)(), C.POINTER(C.c_float)()
         st = L.lm_search_scores(self.h, qb, C.byref(sg), C.byref(n), C.byref(q), C.byref(g), C.byref(s))
-        if st != 0:
-            self._err(st)
+        self._err(st)
         k = n.value
         out = (np.ctypeslib.as_array(q, shape=(k,)).copy() if k else np.zeros(0, np.uint32),
                np.ctypeslib.as_array(g, shape=(k,)).copy() if k else np.zeros(0, np.uint64),
@@ -905,8 +890,7 @@ class Index:
         res = C.c_void_p()
         st = L.lm_search_resident_keep(self.h, qb, kq.ctypes.data_as(C.POINTER(C.c_uint32)),
                                        kg.ctypes.data_as(C.POINTER(C.c_uint64)), len(kq), C.byref(res))
-        if st != 0:
-            self._err(st)
+        self._err(st)
         out = self._collect(res)
         L.lm_result_free(res)
         return out
@@ -930,8 +914,7 @@ class Index:
         arr, keep = _queries(seqs)
         res = C.c_void_p()
         st = L.lm_search_batch(self.h, arr, len(seqs), C.byref(res))
-        if st != 0:
-            self._err(st)
+        self._err(st)
         out = self._collect(res)
         L.lm_result_free(res)
         return out
@@ -941,8 +924,7 @@ class Index:
         arr, keep = _queries(seqs)
         res = C.c_void_p()
         st = L.lm_search_batch(self.h, arr, len(seqs), C.byref(res))
-        if st != 0:
-            self._err(st)
+        self._err(st)
         rows_p = C.POINTER(Hsp)()
         n = L.lm_result_rows(res, C.byref(rows_p))
         size = 1 << 22 if more_columns else 1 << 16
@@ -961,8 +943,7 @@ class Index:
         arr, keep = _queries(seqs)
         sg, km, lo, lc = C.c_void_p(), C.POINTER(C.c_uint64)(), C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)()
         st = L.lm_mask_batch(self.h, arr, len(seqs), C.byref(sg), C.byref(km), C.byref(lo), C.byref(lc))
-        if st != 0:
-            self._err(st)
+        self._err(st)
         M = self.info()["masks"]
         n = len(seqs) * M
         kmers = [km[i] for i in range(n)]
@@ -979,8 +960,7 @@ class Index:
         cptr, cidx = C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)()
         st = L.lm_seed_chain_batch(self.h, arr, len(seqs), C.byref(sg), C.byref(npairs), C.byref(pairs), C.byref(raw),
                                    C.byref(clr), C.byref(cptr), C.byref(cidx))
-        if st != 0:
-            self._err(st)
+        self._err(st)
         out = []
         tup = lambda a: (a.qbegin, a.tbegin, a.len, a.qrc, a.trc)
         for i in range(npairs.value):
@@ -1007,8 +987,7 @@ class Index:
         sg, ro, rv = C.c_void_p(), C.POINTER(C.c_int64)(), C.POINTER(Chain2)()
         st = L.lm_pseudoalign_batch(self.h, qarr, len(queries), tarr, qi, qb, qe, n, C.byref(sg), C.byref(ro),
                                     C.byref(rv))
-        if st != 0:
-            self._err(st)
+        self._err(st)
         out = []
         for i in range(n):
             out.append([{f[0]: getattr(rv[j], f[0]) for f in Chain2._fields_} for j in range(ro[i], ro[i + 1])])
@@ -1040,8 +1019,7 @@ class Index:
         ao, av = C.POINTER(C.c_int64)(), C.POINTER(Anchor)()
         st = L.lm_pseudoalign_batch_ex(self.h, qarr, len(queries), tarr, qi, qb, qe, n, C.byref(sg), C.byref(ro), C.byref(rv),
                                        C.byref(ao), C.byref(av))
-        if st != 0:
-            self._err(st)
+        self._err(st)
         out = self._chains_and_anchors(n, ro, rv, ao, av)
         L.lm_stage_free(sg)
         return out
@@ -1061,10 +1039,7 @@ class Index:
         ao, av = C.POINTER(C.c_int64)(), C.POINTER(Anchor)()
         st = L.lm_pseudoalign_regions(self.h, qarr, len(queries), arr, n, C.byref(sg), C.byref(ro), C.byref(rv), C.byref(ao),
                                       C.byref(av))
-        if st == LM_ERR_ARG:
-            raise ValueError(L.lm_last_error(self.h).decode())
-        if st != 0:
-            self._err(st)
+        self._err(st, REFUSED_ARG)
         out = self._chains_and_anchors(n, ro, rv, ao, av)
         L.lm_stage_free(sg)
         return out
@@ -1075,8 +1050,7 @@ class Index:
         tarr, k2 = _queries([p[1] for p in pairs])
         sg, rv, ops = C.c_void_p(), C.POINTER(Wfa)(), C.POINTER(C.c_uint64)()
         st = L.lm_wfa_batch(self.h, qarr, tarr, len(pairs), C.byref(sg), C.byref(rv), C.byref(ops))
-        if st != 0:
-            self._err(st)
+        self._err(st)
         out = []
         for i in range(len(pairs)):
             r = rv[i]
@@ -1127,20 +1101,13 @@ class IndexBuilder:
         res = C.byref(residency) if residency is not None else None
         if masks is None:
             st = L.lm_index_builder_new(C.byref(self.bo), C.byref(self.opt), res, device, C.byref(h))
-            if st != 0:
-                e = RuntimeError("lm_index_builder_new failed (%d): %s" % (st, L.lm_last_error(None).decode()))
-                e.status = st
-                raise e
+            _check(st, _global_error, "lm_index_builder_new failed (%(status)d): %(text)s")
         else:
             import numpy as np
             ms = np.ascontiguousarray(masks, dtype=np.uint64).reshape(-1)  # (the library copies them before it returns)
             st = L.lm_index_builder_new_masks(C.byref(self.bo), ms.ctypes.data_as(C.POINTER(C.c_uint64)), ms.size, C.byref(self.opt),
                                               res, device, C.byref(h))
-            if st != 0:
-                text = L.lm_last_error(None).decode()
-                e = ValueError(text) if st == 7 else RuntimeError("lm_index_builder_new_masks failed (%d): %s" % (st, text))
-                e.status = st
-                raise e
+            _check(st, _global_error, "lm_index_builder_new_masks failed (%(status)d): %(text)s", REFUSED_ARG)
         self.h = h
 
     @classmethod
@@ -1155,10 +1122,7 @@ class IndexBuilder:
         h = C.c_void_p()
         st = L.lm_index_builder_extend(index.h, C.byref(build_opt) if build_opt is not None else None,
                                        C.byref(residency) if residency is not None else None, C.byref(h))
-        if st != 0:
-            e = RuntimeError("lm_index_builder_extend failed (%d): %s" % (st, L.lm_last_error(None).decode()))
-            e.status = st
-            raise e
+        _check(st, _global_error, "lm_index_builder_extend failed (%(status)d): %(text)s")
         self.h = h
         return self
 
@@ -1173,10 +1137,7 @@ class IndexBuilder:
         h = C.c_void_p()
         st = L.lm_index_builder_like(index.h, C.byref(build_opt) if build_opt is not None else None,
                                      C.byref(residency) if residency is not None else None, C.byref(h))
-        if st != 0:
-            e = RuntimeError("lm_index_builder_like failed (%d): %s" % (st, L.lm_last_error(None).decode()))
-            e.status = st
-            raise e
+        _check(st, _global_error, "lm_index_builder_like failed (%(status)d): %(text)s")
         self.h = h
         return self
 
@@ -1201,10 +1162,7 @@ class IndexBuilder:
 
     def add_index(self, index, keep=None):
         st = self.try_add_index(index, keep)
-        if st == 7:
-            raise ValueError(self.last_error())
-        if st != 0:
-            raise RuntimeError("lm_index_builder_add_index failed (%d): %s" % (st, self.last_error()))
+        _check(st, self.last_error, "lm_index_builder_add_index failed (%(status)d): %(text)s", REFUSED_ARG)
         return self
 
     def try_add(self, genome_id, contigs):
@@ -1223,10 +1181,7 @@ class IndexBuilder:
 
     def add(self, genome_id, contigs):
         st = self.try_add(genome_id, contigs)
-        if st == 7:
-            raise ValueError(self.last_error())
-        if st != 0:
-            raise RuntimeError("lm_index_builder_add failed (%d): %s" % (st, self.last_error()))
+        _check(st, self.last_error, "lm_index_builder_add failed (%(status)d): %(text)s", REFUSED_ARG)
 
     def finish(self):
         """lm_index_builder_finish: the builder is consumed whether it succeeds or not"""
@@ -1234,10 +1189,7 @@ class IndexBuilder:
         h = C.c_void_p()
         bh, self.h = self.h, None
         st = L.lm_index_builder_finish(bh, C.byref(h))
-        if st != 0:
-            e = RuntimeError("lm_index_builder_finish failed (%d): %s" % (st, L.lm_last_error(None).decode()))
-            e.status = st
-            raise e
+        _check(st, _global_error, "lm_index_builder_finish failed (%(status)d): %(text)s")
         return Index(None, self.opt, self.device, _handle=h)
 
     def close(self):
@@ -1313,8 +1265,7 @@ def format_rows(rows, ids, lens, flags=0, want_text=True):
     t0 = time.time()
     st = L.lm_format_rows(arr.ctypes.data_as(C.POINTER(Hsp)), len(arr), idarr, lnarr, len(ids), flags, C.byref(text), C.byref(n))
     dt = time.time() - t0
-    if st != 0:
-        raise RuntimeError("lm_format_rows failed (%d)" % st)
+    _check(st, "", "lm_format_rows failed (%(status)d)")
     out = C.string_at(text, n.value) if want_text else None
     L.lm_free(text)
     return (out if want_text else n.value), dt
@@ -1373,15 +1324,11 @@ def merge_pair_rows(parts):
                 arr[i] = PairRow(d["key1"], d["key2"], g1, g2, d["n_masks"], d["sum_prefix"])
             h = C.c_void_p()
             st = L.lm_pairs_from_rows(arr, len(rows), None, C.byref(h))
-            if st != 0:
-                raise RuntimeError("lm_pairs_from_rows: status %d" % st)
+            _check(st, "", "lm_pairs_from_rows: status %(status)d")
             handles.append(h)
         hs = (C.c_void_p * max(len(handles), 1))(*[h.value for h in handles])
         st = L.lm_pairs_merge(hs, len(handles), C.byref(merged))
-        if st == 7:
-            raise ValueError(L.lm_last_error(None).decode())
-        if st != 0:
-            raise RuntimeError("lm_pairs_merge: status %d" % st)
+        _check(st, _global_error, "lm_pairs_merge: status %(status)d", REFUSED_ARG)
         rows_p = C.POINTER(PairRow)()
         nr = L.lm_pairs_rows(merged, C.byref(rows_p))
         return [{f[0]: getattr(rows_p[i], f[0]) for f in PairRow._fields_} for i in range(nr)]
@@ -1443,8 +1390,7 @@ def format_subseqs(sub, rows=None, ids=None, lens=None, line_width=60):
         nq = len(ids)
     text, n = C.c_void_p(), C.c_size_t(0)
     st = L.lm_format_subseqs(sub.h, rp, idarr, lnarr, nq, line_width, C.byref(text), C.byref(n))
-    if st != 0:
-        raise RuntimeError("lm_format_subseqs failed (%d)" % st)
+    _check(st, "", "lm_format_subseqs failed (%(status)d)")
     out = C.string_at(text, n.value)
     L.lm_free(text)
     return out
@@ -1481,19 +1427,22 @@ class Comm:
     torch.distributed broadcast); every rank then opens Comm(id, nranks, rank, device)."""
 
     @staticmethod
+    def _error(h):
+        """what _check calls for the text of a failed communicator call (h None: a call without a communicator)"""
+        return lambda: (lib().lm_comm_last_error(h) or b"").decode()
+
+    @staticmethod
     def unique_id():
         buf = C.create_string_buffer(COMM_ID_BYTES)
         st = lib().lm_comm_unique_id(buf)
-        if st != 0:
-            raise RuntimeError("lm_comm_unique_id failed (%d): %s" % (st, (lib().lm_comm_last_error(None) or b"").decode()))
+        _check(st, Comm._error(None), "lm_comm_unique_id failed (%(status)d): %(text)s")
         return buf.raw
 
     def __init__(self, uid, nranks, rank, device=0):
         self.L = lib()
         h = C.c_void_p()
         st = self.L.lm_comm_init(bytes(uid), nranks, rank, device, C.byref(h))
-        if st != 0:
-            raise RuntimeError("lm_comm_init failed (%d): %s" % (st, (self.L.lm_comm_last_error(None) or b"").decode()))
+        _check(st, Comm._error(None), "lm_comm_init failed (%(status)d): %(text)s")
         self.h = h
         self.nranks, self.rank = nranks, rank
 
@@ -1514,8 +1463,7 @@ class Comm:
         cnt = (C.c_size_t * self.nranks)()
         st = self.L.lm_gather_rows_ex(self.h, arr.ctypes.data_as(C.POINTER(Hsp)), len(arr), root, LM_ROW_ALL if strings else 0,
                                       C.byref(allp), cnt)
-        if st != 0:
-            raise RuntimeError("lm_gather_rows failed (%d): %s" % (st, (self.L.lm_comm_last_error(self.h) or b"").decode()))
+        _check(st, Comm._error(self.h), "lm_gather_rows failed (%(status)d): %(text)s")
         counts = [int(x) for x in cnt]
         if self.rank != root:
             return None, counts
@@ -1547,8 +1495,7 @@ class Comm:
             st = self.L.lm_merge_sharded_device_ex(self.h, index.h if index is not None else None, C.c_void_p(int(dev_ptr)), cnt,
                                                    C.c_void_p(int(strings_ptr)), int(string_bytes), len(counts), LM_ROW_ALL,
                                                    C.byref(outp), C.byref(total))
-        if st != 0:
-            raise RuntimeError("lm_merge_sharded_device failed (%d): %s" % (st, (self.L.lm_comm_last_error(self.h) or b"").decode()))
+        _check(st, Comm._error(self.h), "lm_merge_sharded_device failed (%(status)d): %(text)s")
         if total.value == 0:
             return np.zeros(0, dtype=ROW_DTYPE)
         buf = (C.c_char * (total.value * C.sizeof(Hsp))).from_address(C.addressof(outp.contents))
@@ -1566,8 +1513,7 @@ class Comm:
         total = C.c_size_t(0)
         st = self.L.lm_gather_merge_rows_ex(self.h, index.h if index is not None else None, arr.ctypes.data_as(C.POINTER(Hsp)), len(arr),
                                             root, LM_ROW_ALL if strings else 0, C.byref(outp), C.byref(total))
-        if st != 0:
-            raise RuntimeError("lm_gather_merge_rows failed (%d): %s" % (st, (self.L.lm_comm_last_error(self.h) or b"").decode()))
+        _check(st, Comm._error(self.h), "lm_gather_merge_rows failed (%(status)d): %(text)s")
         if self.rank != root:
             return None
         if total.value == 0:

@@ -38,6 +38,14 @@ struct HipError : std::runtime_error {
 struct DeviceOOM : HipError {
     explicit DeviceOOM(const std::string &m) : HipError(m) {}
 };
+// What an entry point refuses before or while it works, the handle staying usable (lm::guarded below): an argument
+// (LM_ERR_ARG) or an option out of range (LM_ERR_OPTION).  The text names the call, so helpers shared by calls throw these too.
+struct ArgError : std::runtime_error {
+    explicit ArgError(const std::string &m) : std::runtime_error(m) {}
+};
+struct OptionError : std::runtime_error {
+    explicit OptionError(const std::string &m) : std::runtime_error(m) {}
+};
 inline std::atomic<int64_t> g_dbuf_bytes{0}; // device bytes held by all DBufs of the process (index image + scratch)
 
 // hipMalloc that leaves the device a reserve.  The runtime allocates device memory of its own while a search runs (kernel
@@ -383,6 +391,16 @@ static inline double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
+// blocks of `block` lanes for one lane per element.  Not for grid-stride kernels, which cap their grids: sp_grid in
+// lm_seedpack.hip, and the file-local grid_for(n, block, maxb) of lm_kernels.hip behind LM_LAUNCH_1D - another function of
+// this name with a cap of 16384 blocks; lm_kernels.hip does not include this header and must not come to call this one.
+inline int grid_for(int64_t n, int block = 256) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + block - 1) / block, (int64_t)1 << 30)); }
+inline int bits_for(int64_t n) { // bits needed for values in [0, n)
+    int b = 1;
+    while (((int64_t)1 << b) < n) b++;
+    return b;
+}
+
 struct ProfEntry {
     std::string name;
     int64_t launches = 0;
@@ -583,4 +601,40 @@ struct BindScope {
     BindScope &operator=(const BindScope &) = delete;
     ~BindScope() { tls_bind = prev; }
 };
+
+// The call guard of the entry points that ask a resident index a question ("Statuses of the resident-index
+// calls"): runs `body` under the handle's mutex on its device; what it throws becomes the status and the handle's error text -
+// what() of the exception, or `who` + `host_nomem_text` when the host ran out of memory (put together only then: a call
+// whose text names it passes its name and the rest apart).  DeviceOOM is a HipError and the refusals are runtime_errors:
+// the order of the arms is the mapping.
+template <class Body> lm_status guarded(lm_index *ix, const char *who, const char *host_nomem_text, Body body) {
+    std::lock_guard<std::mutex> lock(ix->mu);
+    try {
+        HIPCHK(hipSetDevice(ix->device));
+        body();
+        return LM_OK;
+    } catch (const ArgError &e) {
+        ix->err = e.what();
+        return LM_ERR_ARG;
+    } catch (const OptionError &e) {
+        ix->err = e.what();
+        return LM_ERR_OPTION;
+    } catch (const DeviceOOM &e) {
+        (void)hipGetLastError();
+        ix->err = e.what();
+        return LM_ERR_NOMEM;
+    } catch (const std::bad_alloc &) {
+        ix->err = std::string(who) + host_nomem_text;
+        return LM_ERR_NOMEM;
+    } catch (const std::exception &e) {
+        ix->err = e.what();
+        return LM_ERR_HIP;
+    }
+}
+template <class Body> lm_status guarded(lm_index *ix, const char *host_nomem_text, Body body) {
+    return guarded(ix, "", host_nomem_text, body);
+}
+
+// the genome ids of records by key, one name lookup per key (beside lm_attach_names, lm_pipeline.hip); the texts stay the handle's
+void genome_ids_of_keys(lm_index *ix, const std::vector<uint64_t> &keys, std::vector<const char *> &ids);
 } // namespace lm

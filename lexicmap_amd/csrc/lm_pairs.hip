@@ -51,13 +51,6 @@
 
 namespace lm {
 
-struct PairArg : std::runtime_error {
-    explicit PairArg(const std::string &m) : std::runtime_error(m) {}
-};
-struct PairOption : std::runtime_error {
-    explicit PairOption(const std::string &m) : std::runtime_error(m) {}
-};
-
 #define PR_RUN 16 /* sorted tuples per lane of k_pair_reduce */
 
 __device__ __forceinline__ int pr_lane_rank(unsigned long long bal) { // kept lanes below this one (mbcnt)
@@ -305,8 +298,6 @@ __global__ void k_pair_order_keys(const unsigned long long *__restrict__ val, in
     if (i < n) key[i] = ~(uint64_t)val[i];
 }
 
-static int pr_grid(int64_t n, int block = 256) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + block - 1) / block, (int64_t)1 << 30)); }
-
 static void pr_max_scan(hipStream_t st, DBuf<uint8_t> &tmp, int64_t *io, size_t n) {
     if (n == 0) return;
     size_t bytes = 0;
@@ -331,12 +322,12 @@ struct PairCross {
 static void pair_take_masks(const HostIndex &h, const std::string &who, int32_t masks, std::vector<int32_t> &sel) {
     std::string why;
     if (masks < 0 || !pair_select_masks(h.masks.data(), h.M, h.k, masks, sel, why))
-        throw PairOption(who + ": " + (masks < 0 ? "masks (" + std::to_string(masks) + ") should be 0 (all masks) or a power of 4 that is >= 64" : why));
+        throw OptionError(who + ": " + (masks < 0 ? "masks (" + std::to_string(masks) + ") should be 0 (all masks) or a power of 4 that is >= 64" : why));
 }
 // the records that take part, as (key, local record), ascending by key
 static std::vector<std::pair<uint64_t, int64_t>> pair_take_records(lm_index *ix, const std::string &who, const uint64_t *keys, size_t nkeys) {
     const HostIndex &h = ix->host;
-    if (!keys && nkeys > 0) throw PairArg(who + ": keys is NULL but nkeys is not 0");
+    if (!keys && nkeys > 0) throw ArgError(who + ": keys is NULL but nkeys is not 0");
     const int64_t nlocal = (int64_t)h.genomes.size();
     std::vector<std::pair<uint64_t, int64_t>> chosen;
     if (!keys) {
@@ -347,10 +338,10 @@ static std::vector<std::pair<uint64_t, int64_t>> pair_take_records(lm_index *ix,
             const auto it = ix->bg2local.find(keys[s]);
             const std::string name = "key " + std::to_string(keys[s]) + " (batch " + std::to_string(keys[s] >> 17) + ", index " + std::to_string(keys[s] & 0x1ffff) + ")";
             if (it == ix->bg2local.end() && h.other_of.count(keys[s]))
-                throw PairArg(who + ": " + name + " is a record of another shard (this handle is shard " + std::to_string(h.shard_rank) + " of " +
+                throw ArgError(who + ": " + name + " is a record of another shard (this handle is shard " + std::to_string(h.shard_rank) + " of " +
                               std::to_string(h.shard_count) + " and selects among its own records)");
-            if (it == ix->bg2local.end()) throw PairArg(who + ": " + name + " is no record of this index");
-            if (taken[(size_t)it->second]) throw PairArg(who + ": " + name + " is given twice");
+            if (it == ix->bg2local.end()) throw ArgError(who + ": " + name + " is no record of this index");
+            if (taken[(size_t)it->second]) throw ArgError(who + ": " + name + " is given twice");
             taken[(size_t)it->second] = 1;
             chosen.emplace_back(keys[s], (int64_t)it->second);
         }
@@ -423,14 +414,14 @@ static void pairs_run(lm_index *ix, const uint64_t *keys, size_t nkeys, const lm
     const double t_begin = now_ms();
     // ---- refusals
     if (!cross && h.shard_count > 1)
-        throw PairArg(who + ": this handle is shard " + std::to_string(h.shard_rank) + " of " + std::to_string(h.shard_count) +
+        throw ArgError(who + ": this handle is shard " + std::to_string(h.shard_rank) + " of " + std::to_string(h.shard_count) +
                       "; a shard does not see the pairs across shards, so the pairs of an index are computed on an unsharded handle");
-    if (!keys && nkeys > 0) throw PairArg(who + ": keys is NULL but nkeys is not 0");
+    if (!keys && nkeys > 0) throw ArgError(who + ": keys is NULL but nkeys is not 0");
     if (opt.min_prefix > K || opt.min_prefix < h.mask_prefix + h.anchor_prefix)
-        throw PairOption(who + ": min_prefix (" + std::to_string(opt.min_prefix) + ") should be in the range of [" +
+        throw OptionError(who + ": min_prefix (" + std::to_string(opt.min_prefix) + ") should be in the range of [" +
                          std::to_string(h.mask_prefix + h.anchor_prefix) + ", " + std::to_string(K) + "]");
     if (!(opt.min_mask_fraction >= 0.0))
-        throw PairOption(who + ": min_mask_fraction (" + std::to_string(opt.min_mask_fraction) + ") should be >= 0");
+        throw OptionError(who + ": min_mask_fraction (" + std::to_string(opt.min_mask_fraction) + ") should be >= 0");
     std::vector<int32_t> sel;
     pair_take_masks(h, who, opt.masks, sel);
     const int32_t ns = (int32_t)sel.size();
@@ -458,12 +449,12 @@ static void pairs_run(lm_index *ix, const uint64_t *keys, size_t nkeys, const lm
         std::string why;
         for (size_t b = 0; b < cross->blobs.size(); b++) {
             const PairBlobView &bv = cross->blobs[b];
-            if (!pair_blob_fits(bv.hd, K, M, fp, opt.masks, ns, why)) throw PairArg(who + ": blob " + std::to_string(b) + ": " + why);
+            if (!pair_blob_fits(bv.hd, K, M, fp, opt.masks, ns, why)) throw ArgError(who + ": blob " + std::to_string(b) + ": " + why);
             bkeys[b].resize((size_t)bv.hd.records);
             if (bv.hd.records) memcpy(bkeys[b].data(), bv.keys, (size_t)bv.hd.records * 8);
             nblob_entries += bv.hd.entries;
         }
-        if (!pair_slot_union(own, bkeys, slots, why)) throw PairArg(who + ": " + why);
+        if (!pair_slot_union(own, bkeys, slots, why)) throw ArgError(who + ": " + why);
         for (int64_t s = 0; s < nown; s++) slot_of_local[(size_t)chosen[(size_t)s].second] = (int32_t)slots.own_slot[(size_t)s];
         out.slot_key = slots.key;
         out.slot_src = slots.src;
@@ -476,7 +467,7 @@ static void pairs_run(lm_index *ix, const uint64_t *keys, size_t nkeys, const lm
         out.stats.ms_total = now_ms() - t_begin;
         return;
     }
-    if (nsel >= ((int64_t)1 << 31)) throw PairArg(who + ": more than 2^31 records");
+    if (nsel >= ((int64_t)1 << 31)) throw ArgError(who + ": more than 2^31 records");
     const int slot_bits = pair_bits(nsel);
     // ---- entries
     PairOwnScan own;
@@ -502,10 +493,10 @@ static void pairs_run(lm_index *ix, const uint64_t *keys, size_t nkeys, const lm
                                 std::to_string((n * 36) >> 20) + " MB) on the device beside the index: " + e.what() + "; select fewer masks or records");
             }
             own.write(ix, e_kmer.p, e_slot.p, e_ms.p);
-            hipLaunchKernelGGL(k_pair_heads, dim3(pr_grid(n)), dim3(256), 0, st, e_kmer.p, e_ms.p, n, (K - opt.min_prefix) << 1, hp.p);
+            hipLaunchKernelGGL(k_pair_heads, dim3(grid_for(n)), dim3(256), 0, st, e_kmer.p, e_ms.p, n, (K - opt.min_prefix) << 1, hp.p);
             HIPCHK(hipGetLastError());
             pr_max_scan(st, tmp, hp.p, (size_t)n);
-            hipLaunchKernelGGL(k_pair_counts, dim3(pr_grid(n + 1)), dim3(256), 0, st, hp.p, n, cnt.p);
+            hipLaunchKernelGGL(k_pair_counts, dim3(grid_for(n + 1)), dim3(256), 0, st, hp.p, n, cnt.p);
             HIPCHK(hipGetLastError());
         } else {
             // own entries, then every blob's: a stable sort by the top min_prefix bases and a stable sort by mask bring the
@@ -530,7 +521,7 @@ static void pairs_run(lm_index *ix, const uint64_t *keys, size_t nkeys, const lm
             if (own.n > 0) { // (k2 / v2 are staging room until the sort)
                 uint32_t *os = (uint32_t *)v2.p, *om = os + own.n;
                 own.write(ix, e_kmer.p, os, om);
-                hipLaunchKernelGGL(k_pair_pack_own, dim3(pr_grid(own.n)), dim3(256), 0, st, os, om, own.n, pk.p);
+                hipLaunchKernelGGL(k_pair_pack_own, dim3(grid_for(own.n)), dim3(256), 0, st, os, om, own.n, pk.p);
                 HIPCHK(hipGetLastError());
             }
             int64_t at = own.n;
@@ -547,7 +538,7 @@ static void pairs_run(lm_index *ix, const uint64_t *keys, size_t nkeys, const lm
                 HIPCHK(hipMemcpyAsync(rec, bv.recs, (size_t)nb * 4, hipMemcpyHostToDevice, st));
                 HIPCHK(hipMemcpyAsync(b_eoff.p, bv.offsets, ((size_t)ns + 1) * 8, hipMemcpyHostToDevice, st));
                 HIPCHK(hipMemcpyAsync(b_slot.p, slots.blob_slot[b].data(), (size_t)bv.hd.records * 4, hipMemcpyHostToDevice, st));
-                hipLaunchKernelGGL(k_pair_pack_blob, dim3(pr_grid(nb)), dim3(256), 0, st, rec, nb, b_eoff.p, ns, b_slot.p, bv.hd.records, pk.p + at);
+                hipLaunchKernelGGL(k_pair_pack_blob, dim3(grid_for(nb)), dim3(256), 0, st, rec, nb, b_eoff.p, ns, b_slot.p, bv.hd.records, pk.p + at);
                 HIPCHK(hipGetLastError());
                 HIPCHK(hipStreamSynchronize(st)); // (b_eoff / b_slot serve the next blob)
                 at += nb;
@@ -561,7 +552,7 @@ static void pairs_run(lm_index *ix, const uint64_t *keys, size_t nkeys, const lm
                 e_slot.alloc_exact((size_t)n);
                 e_ms.alloc_exact((size_t)n);
                 ownf.alloc_exact((size_t)n + 1);
-                hipLaunchKernelGGL(k_pair_unpack, dim3(pr_grid(n + 1)), dim3(256), 0, st, pk.p, n, e_slot.p, e_ms.p, ownf.p);
+                hipLaunchKernelGGL(k_pair_unpack, dim3(grid_for(n + 1)), dim3(256), 0, st, pk.p, n, e_slot.p, e_ms.p, ownf.p);
                 HIPCHK(hipGetLastError());
                 HIPCHK(hipStreamSynchronize(st));
                 pk.release();
@@ -573,19 +564,19 @@ static void pairs_run(lm_index *ix, const uint64_t *keys, size_t nkeys, const lm
             } catch (const DeviceOOM &e) {
                 throw oom(e, 49);
             }
-            hipLaunchKernelGGL(k_pair_heads, dim3(pr_grid(n)), dim3(256), 0, st, e_kmer.p, e_ms.p, n, (K - opt.min_prefix) << 1, hp.p);
+            hipLaunchKernelGGL(k_pair_heads, dim3(grid_for(n)), dim3(256), 0, st, e_kmer.p, e_ms.p, n, (K - opt.min_prefix) << 1, hp.p);
             HIPCHK(hipGetLastError());
             pr_max_scan(st, tmp, hp.p, (size_t)n);
             prim_scan_to_i64(st, tmp, ownf.p, (size_t)n, ownx.p);
-            hipLaunchKernelGGL(k_pair_counts_two, dim3(pr_grid(n + 1)), dim3(256), 0, st, hp.p, ownx.p, n, cnt.p, back.p);
+            hipLaunchKernelGGL(k_pair_counts_two, dim3(grid_for(n + 1)), dim3(256), 0, st, hp.p, ownx.p, n, cnt.p, back.p);
             HIPCHK(hipGetLastError());
             HIPCHK(hipStreamSynchronize(st)); // (ownf / ownx end here)
         }
         prim_scan_to_i64(st, tmp, cnt.p, (size_t)n, offs.p);
         ceoff.alloc_exact((size_t)ns + 1);
         d_tot.alloc_exact((size_t)ns);
-        hipLaunchKernelGGL(k_pair_mask_bounds, dim3(pr_grid(n + 1)), dim3(256), 0, st, e_ms.p, n, ns, ceoff.p);
-        hipLaunchKernelGGL(k_pair_mask_totals, dim3(pr_grid(ns)), dim3(256), 0, st, ceoff.p, offs.p, ns, d_tot.p);
+        hipLaunchKernelGGL(k_pair_mask_bounds, dim3(grid_for(n + 1)), dim3(256), 0, st, e_ms.p, n, ns, ceoff.p);
+        hipLaunchKernelGGL(k_pair_mask_totals, dim3(grid_for(ns)), dim3(256), 0, st, ceoff.p, offs.p, ns, d_tot.p);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(h_ceoff.data(), ceoff.p, h_ceoff.size() * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(h_tot.data(), d_tot.p, h_tot.size() * 8, hipMemcpyDeviceToHost, st));
@@ -605,7 +596,7 @@ static void pairs_run(lm_index *ix, const uint64_t *keys, size_t nkeys, const lm
     int32_t bad = 0;
     if (!pair_pieces(h_tot.data(), ns, soft, hard, slot_bits, pieces, &bad)) {
         if (bad < 0)
-            throw PairArg(std::string(who) + ": two of " + std::to_string((long long)nsel) + " record slots and a length do not fit a 64-bit tuple: select at most 2^29 records");
+            throw ArgError(std::string(who) + ": two of " + std::to_string((long long)nsel) + " record slots and a length do not fit a 64-bit tuple: select at most 2^29 records");
         throw DeviceOOM(std::string(who) + ": mask " + std::to_string(sel[(size_t)bad]) + " alone gives " + std::to_string((long long)h_tot[(size_t)bad]) +
                         " candidate seed pairs; at " + std::to_string((long long)per_tuple) + " B each the tuples of one mask must fit the " +
                         std::to_string(fr_b >> 20) + " MB free beside the index: select fewer records or a longer min_prefix");
@@ -636,7 +627,7 @@ static void pairs_run(lm_index *ix, const uint64_t *keys, size_t nkeys, const lm
         fk.ensure((size_t)nc + 1);
         pos_h.ensure((size_t)nc + 1);
         pos_k.ensure((size_t)nc + 1);
-        hipLaunchKernelGGL(k_pair_merge_flags, dim3(pr_grid(nc + 1)), dim3(256), 0, st, sp, sv, nc, masks_left, required, fh.p, fk.p);
+        hipLaunchKernelGGL(k_pair_merge_flags, dim3(grid_for(nc + 1)), dim3(256), 0, st, sp, sv, nc, masks_left, required, fh.p, fk.p);
         HIPCHK(hipGetLastError());
         prim_scan_to_i64(st, tmp, fh.p, (size_t)nc, pos_h.p);
         prim_scan_to_i64(st, tmp, fk.p, (size_t)nc, pos_k.p);
@@ -647,7 +638,7 @@ static void pairs_run(lm_index *ix, const uint64_t *keys, size_t nkeys, const lm
         out.stats.pairs_seen += heads - nt; // pairs the table did not hold before this piece
         tab_pair.ensure((size_t)std::max<int64_t>(kept, 1));
         tab_val.ensure((size_t)std::max<int64_t>(kept, 1));
-        hipLaunchKernelGGL(k_pair_merge_scatter, dim3(pr_grid(nc)), dim3(256), 0, st, sp, sv, nc, fk.p, pos_k.p, tab_pair.p, tab_val.p);
+        hipLaunchKernelGGL(k_pair_merge_scatter, dim3(grid_for(nc)), dim3(256), 0, st, sp, sv, nc, fk.p, pos_k.p, tab_pair.p, tab_val.p);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(st));
         nt = kept;
@@ -682,7 +673,7 @@ static void pairs_run(lm_index *ix, const uint64_t *keys, size_t nkeys, const lm
         const double tb = now_ms();
         out.stats.ms_emit += tb - ta;
         prim_sort_keys(st, tmp, tk.p, tk2.p, (size_t)nall, 0, key_bits);
-        hipLaunchKernelGGL(k_pair_flags, dim3(pr_grid(nall + 1)), dim3(256), 0, st, tk2.p, nall, pair_shift, fr.p);
+        hipLaunchKernelGGL(k_pair_flags, dim3(grid_for(nall + 1)), dim3(256), 0, st, tk2.p, nall, pair_shift, fr.p);
         HIPCHK(hipGetLastError());
         prim_scan_to_i64(st, tmp, fr.p, (size_t)nall, orr.p);
         int64_t nr = 0;
@@ -701,7 +692,7 @@ static void pairs_run(lm_index *ix, const uint64_t *keys, size_t nkeys, const lm
         }
         if (nr > 0) {
             HIPCHK(hipMemsetAsync(cat_val.p + nt, 0, (size_t)nr * 8, st));
-            hipLaunchKernelGGL(k_pair_reduce, dim3(pr_grid((nall + PR_RUN - 1) / PR_RUN)), dim3(256), 0, st, tk2.p, nall, pair_shift, fr.p, orr.p,
+            hipLaunchKernelGGL(k_pair_reduce, dim3(grid_for((nall + PR_RUN - 1) / PR_RUN)), dim3(256), 0, st, tk2.p, nall, pair_shift, fr.p, orr.p,
                                cat_pair.p + nt, cat_val.p + nt);
             HIPCHK(hipGetLastError());
         }
@@ -727,7 +718,7 @@ static void pairs_run(lm_index *ix, const uint64_t *keys, size_t nkeys, const lm
         cat_val.ensure((size_t)nt);
         cat_val2.ensure((size_t)nt);
         uint64_t *okey = cat_pair.p, *okey2 = cat_pair2.p;
-        hipLaunchKernelGGL(k_pair_order_keys, dim3(pr_grid(nt)), dim3(256), 0, st, tab_val.p, nt, okey);
+        hipLaunchKernelGGL(k_pair_order_keys, dim3(grid_for(nt)), dim3(256), 0, st, tab_val.p, nt, okey);
         HIPCHK(hipGetLastError());
         prim_sort_pairs(st, tmp, okey, okey2, tab_pair.p, (uint64_t *)cat_val2.p, (size_t)nt, 0, 64);
         std::vector<uint64_t> hk((size_t)nt), hp((size_t)nt);
@@ -760,45 +751,8 @@ extern "C" void lm_pair_opt_default(lm_pair_opt *o) {
     o->min_mask_fraction = 0.25;
 }
 
-// runs `body` under the handle's mutex on its device; what it throws becomes the status and the handle's error text
-template <typename F> static lm_status pairs_guard(lm_index *ix, const char *who, F body) {
-    using namespace lm;
-    std::lock_guard<std::mutex> lock(ix->mu);
-    try {
-        HIPCHK(hipSetDevice(ix->device));
-        body();
-    } catch (const lm::PairArg &e) {
-        ix->err = e.what();
-        return LM_ERR_ARG;
-    } catch (const lm::PairOption &e) {
-        ix->err = e.what();
-        return LM_ERR_OPTION;
-    } catch (const DeviceOOM &e) {
-        (void)hipGetLastError();
-        ix->err = e.what();
-        return LM_ERR_NOMEM;
-    } catch (const std::bad_alloc &) {
-        ix->err = std::string(who) + ": the host could not hold the selection or the rows";
-        return LM_ERR_NOMEM;
-    } catch (const std::exception &e) {
-        ix->err = e.what();
-        return LM_ERR_HIP;
-    }
-    return LM_OK;
-}
-
-// the ids of own records, by key: one lookup per record
-static void pairs_own_names(lm_index *ix, const std::vector<uint64_t> &keys, std::vector<const char *> &ids) {
-    std::vector<lm_hsp> names(keys.size());
-    for (size_t i = 0; i < keys.size(); i++) {
-        memset(&names[i], 0, sizeof names[i]);
-        names[i].batch_genome = keys[i];
-        names[i].seq_idx = -1;
-    }
-    lm_attach_names(ix, names.data(), names.size());
-    ids.resize(keys.size());
-    for (size_t i = 0; i < keys.size(); i++) ids[i] = names[i].genome_id;
-}
+// lm::guarded's text, behind the call's name, for a host that ran out of memory: every call of this file
+static const char *const PAIRS_NOMEM = ": the host could not hold the selection or the rows";
 
 // lm_index_genome_pairs (cross == nullptr) and lm_index_genome_pairs_across
 static lm_status pairs_call(lm_index *ix, const char *who, const uint64_t *keys, size_t nkeys, const lm_pair_opt *opt_in, const lm::PairCross *cross,
@@ -809,7 +763,7 @@ static lm_status pairs_call(lm_index *ix, const char *who, const uint64_t *keys,
     if (opt_in) opt = *opt_in;
     std::unique_ptr<lm_pairs> res(new lm_pairs());
     memset(&res->stats, 0, sizeof res->stats);
-    const lm_status rc = pairs_guard(ix, who, [&]() {
+    const lm_status rc = guarded(ix, who, PAIRS_NOMEM, [&]() {
         PairOut po;
         memset(&po.stats, 0, sizeof po.stats);
         pairs_run(ix, keys, nkeys, opt, cross, po);
@@ -827,7 +781,7 @@ static lm_status pairs_call(lm_index *ix, const char *who, const uint64_t *keys,
                 own_keys.push_back(po.slot_key[s]);
             }
         }
-        pairs_own_names(ix, own_keys, name);
+        genome_ids_of_keys(ix, own_keys, name);
         for (size_t s = 0; s < used.size(); s++) {
             if (!used[s] || name_of[s] >= 0) continue;
             const size_t b = (size_t)po.slot_src[s];
@@ -900,7 +854,7 @@ extern "C" lm_status lm_index_pair_seeds(lm_index *ix, const uint64_t *keys, siz
     lm_pair_opt opt;
     lm_pair_opt_default(&opt);
     if (opt_in) opt = *opt_in;
-    return pairs_guard(ix, who.c_str(), [&]() {
+    return guarded(ix, who.c_str(), PAIRS_NOMEM, [&]() {
         const hipStream_t st = ix->lane[0].main.st;
         const HostIndex &h = ix->host;
         std::vector<int32_t> sel;
@@ -908,7 +862,7 @@ extern "C" lm_status lm_index_pair_seeds(lm_index *ix, const uint64_t *keys, siz
         const int32_t ns = (int32_t)sel.size();
         const std::vector<std::pair<uint64_t, int64_t>> chosen = pair_take_records(ix, who, keys, nkeys);
         const int64_t nrec = (int64_t)chosen.size();
-        if (nrec > LM_PAIR_MAX_SLOTS) throw PairArg(who + ": more than 2^29 records");
+        if (nrec > LM_PAIR_MAX_SLOTS) throw ArgError(who + ": more than 2^29 records");
         // slots in ascending key order: a seed's slot is its record's index in the blob
         std::vector<int32_t> slot_of_local(h.genomes.size(), -1);
         std::vector<uint64_t> rkeys((size_t)nrec);
@@ -937,7 +891,7 @@ extern "C" lm_status lm_index_pair_seeds(lm_index *ix, const uint64_t *keys, siz
                 }
                 own.write(ix, e_kmer.p, e_slot.p, e_ms.p);
                 ceoff.alloc_exact((size_t)ns + 1);
-                hipLaunchKernelGGL(k_pair_mask_bounds, dim3(pr_grid(n + 1)), dim3(256), 0, st, e_ms.p, n, ns, ceoff.p);
+                hipLaunchKernelGGL(k_pair_mask_bounds, dim3(grid_for(n + 1)), dim3(256), 0, st, e_ms.p, n, ns, ceoff.p);
                 HIPCHK(hipGetLastError());
                 kmers.resize((size_t)n);
                 recs.resize((size_t)n);
@@ -949,7 +903,7 @@ extern "C" lm_status lm_index_pair_seeds(lm_index *ix, const uint64_t *keys, siz
             ix->lane[0].main.tmp.release();
         }
         std::vector<const char *> idp;
-        pairs_own_names(ix, rkeys, idp);
+        genome_ids_of_keys(ix, rkeys, idp);
         std::vector<std::string> ids((size_t)nrec);
         PairBlobHead hd;
         hd.k = h.k;
@@ -969,7 +923,7 @@ extern "C" lm_status lm_index_pair_seeds(lm_index *ix, const uint64_t *keys, siz
         std::string why;
         if (!pair_blob_write(hd, rkeys.data(), ids, offsets.data(), kmers.data(), recs.data(), p, why)) {
             free(p);
-            throw PairArg(who + ": " + why);
+            throw ArgError(who + ": " + why);
         }
         *blob = p;
         *bytes = nb;

@@ -4313,6 +4313,17 @@ void lm_attach_names(lm_index *ix, lm_hsp *rows, size_t n) {
         }
     });
 }
+extern "C++" void lm::genome_ids_of_keys(lm_index *ix, const std::vector<uint64_t> &keys, std::vector<const char *> &ids) {
+    std::vector<lm_hsp> names(keys.size());
+    for (size_t i = 0; i < keys.size(); i++) {
+        memset(&names[i], 0, sizeof names[i]);
+        names[i].batch_genome = keys[i];
+        names[i].seq_idx = -1;
+    }
+    lm_attach_names(ix, names.data(), names.size());
+    ids.resize(keys.size());
+    for (size_t i = 0; i < keys.size(); i++) ids[i] = names[i].genome_id;
+}
 
 // ---- merging the rows of genome shards ------------------------------------------------------------
 // Host-only: no device work, callable without a GPU (idx may be NULL: names are then left NULL).

@@ -42,13 +42,6 @@
 
 namespace lm {
 
-struct ScreenArg : std::runtime_error {
-    explicit ScreenArg(const std::string &m) : std::runtime_error(m) {}
-};
-struct ScreenOption : std::runtime_error {
-    explicit ScreenOption(const std::string &m) : std::runtime_error(m) {}
-};
-
 #define SC_LEN_BITS 6   /* Len <= 32 */
 #define SC_MASK_BITS 16 /* masks <= 65535 */
 #define SC_REC_SHIFT (SC_LEN_BITS + SC_MASK_BITS)
@@ -303,13 +296,6 @@ __global__ __launch_bounds__(256) void k_screen_reduce(const uint64_t *__restric
     flush();
 }
 
-static int sc_grid(int64_t n, int block = 256) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + block - 1) / block, (int64_t)1 << 30)); }
-static int sc_bits(int64_t n) {
-    int b = 1;
-    while (((int64_t)1 << b) < n) b++;
-    return b;
-}
-
 struct ScreenOut {
     std::vector<ScreenPartial> partials;
     std::vector<uint8_t> prefs;
@@ -379,7 +365,7 @@ static void screen_sub_batch(lm_index *ix, const lm_genome_query *queries, const
     lk_slot.alloc_exact((size_t)nslots);
     ctr.alloc_exact(1, true, st);
     per_mask.alloc_exact((size_t)3 * M, true, st);
-    hipLaunchKernelGGL(k_screen_prep, dim3(sc_grid(nslots)), dim3(256), 0, st, v, d_kmers.p, d_rec_first.p, nslots, lk_key.p, lk_slot.p, ctr.p);
+    hipLaunchKernelGGL(k_screen_prep, dim3(grid_for(nslots)), dim3(256), 0, st, v, d_kmers.p, d_rec_first.p, nslots, lk_key.p, lk_slot.p, ctr.p);
     HIPCHK(hipGetLastError());
     unsigned long long nlk_u = 0;
     HIPCHK(hipMemcpyAsync(&nlk_u, ctr.p, sizeof nlk_u, hipMemcpyDeviceToHost, st));
@@ -407,7 +393,7 @@ static void screen_sub_batch(lm_index *ix, const lm_genome_query *queries, const
     counts.alloc_exact((size_t)nlk + 1, true, st);
     starts.alloc_exact((size_t)nlk);
     offs.alloc_exact((size_t)nlk + 1);
-    hipLaunchKernelGGL(k_screen_count, dim3(sc_grid(nlk)), dim3(256), 0, st, v, d_kmers.p, lk_key2.p, lk_slot2.p, nlk, opt.min_prefix, counts.p,
+    hipLaunchKernelGGL(k_screen_count, dim3(grid_for(nlk)), dim3(256), 0, st, v, d_kmers.p, lk_key2.p, lk_slot2.p, nlk, opt.min_prefix, counts.p,
                        starts.p, per_mask.p,
                        ix->sc_set ? ScreenShadowTab{ix->d_sc_bits.p, ix->d_sc_sum.p, ix->d_sc_kmers.p, ix->d_sc_off.p, ix->sc_W}
                                   : ScreenShadowTab{nullptr, nullptr, nullptr, nullptr, 0});
@@ -417,10 +403,10 @@ static void screen_sub_batch(lm_index *ix, const lm_genome_query *queries, const
     HIPCHK(hipMemcpyAsync(pm.data(), per_mask.p, pm.size() * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     // ---- pieces of whole masks
-    const int qbits = sc_bits((int64_t)q1), gbits = sc_bits(std::max<int64_t>(v.ngenomes, 2));
+    const int qbits = bits_for((int64_t)q1), gbits = bits_for(std::max<int64_t>(v.ngenomes, 2));
     const int qshift = SC_REC_SHIFT + gbits;
     if (qshift + qbits > 64)
-        throw ScreenArg("lm_index_screen_genomes: " + std::to_string(q1) + " queries against " + std::to_string((long long)v.ngenomes) +
+        throw ArgError("lm_index_screen_genomes: " + std::to_string(q1) + " queries against " + std::to_string((long long)v.ngenomes) +
                         " records do not fit the 42 bits a tuple has for both: screen fewer queries per call");
     size_t fr = 0, tot = 0;
     HIPCHK(hipMemGetInfo(&fr, &tot));
@@ -464,7 +450,7 @@ static void screen_sub_batch(lm_index *ix, const lm_genome_query *queries, const
             throw DeviceOOM("lm_index_screen_genomes: the " + std::to_string((long long)n_all) + " tuples of masks " + std::to_string(P.m0) + " .. " +
                             std::to_string(P.m1 - 1) + " need 34 B each on the device beside the index: " + e.what());
         }
-        hipLaunchKernelGGL(k_screen_emit, dim3(sc_grid(j1 - j0)), dim3(256), 0, st, v, d_kmers.p, d_rec2q.p, lk_key2.p, lk_slot2.p, j0, j1, counts.p,
+        hipLaunchKernelGGL(k_screen_emit, dim3(grid_for(j1 - j0)), dim3(256), 0, st, v, d_kmers.p, d_rec2q.p, lk_key2.p, lk_slot2.p, j0, j1, counts.p,
                            offs.p, starts.p, qshift, tk.p);
         HIPCHK(hipGetLastError());
         if (dbg) HIPCHK(hipStreamSynchronize(st));
@@ -472,7 +458,7 @@ static void screen_sub_batch(lm_index *ix, const lm_genome_query *queries, const
         t_emit += tb - ta;
         if (n == 0) continue;
         prim_sort_keys(st, tmp, tk.p, tk2.p, (size_t)n_all, 0, std::min(64, qshift + qbits));
-        hipLaunchKernelGGL(k_screen_flags, dim3(sc_grid(n + 1)), dim3(256), 0, st, tk2.p, n, fm.p, frr.p);
+        hipLaunchKernelGGL(k_screen_flags, dim3(grid_for(n + 1)), dim3(256), 0, st, tk2.p, n, fm.p, frr.p);
         HIPCHK(hipGetLastError());
         prim_scan_to_i64(st, tmp, fm.p, (size_t)n, om.p);
         prim_scan_to_i64(st, tmp, frr.p, (size_t)n, orr.p);
@@ -483,7 +469,7 @@ static void screen_sub_batch(lm_index *ix, const lm_genome_query *queries, const
         d_rows.ensure((size_t)ngr);
         HIPCHK(hipMemsetAsync(d_rows.p, 0, (size_t)ngr * sizeof(ScreenRowDev), st));
         if (opt.details) d_prefs.ensure((size_t)ngm);
-        hipLaunchKernelGGL(k_screen_reduce, dim3(sc_grid((n + SC_RUN - 1) / SC_RUN)), dim3(256), 0, st, tk2.p, n, fm.p, frr.p, om.p, orr.p, d_rows.p,
+        hipLaunchKernelGGL(k_screen_reduce, dim3(grid_for((n + SC_RUN - 1) / SC_RUN)), dim3(256), 0, st, tk2.p, n, fm.p, frr.p, om.p, orr.p, d_rows.p,
                            opt.details ? d_prefs.p : nullptr);
         HIPCHK(hipGetLastError());
         hrows.resize((size_t)ngr);
@@ -537,30 +523,28 @@ extern "C" lm_status lm_index_screen_genomes(lm_index *ix, const lm_genome_query
     if (opt_in) opt = *opt_in;
     std::unique_ptr<lm_screen> res(new lm_screen());
     memset(&res->stats, 0, sizeof res->stats);
-    std::lock_guard<std::mutex> lock(ix->mu);
-    try {
-        HIPCHK(hipSetDevice(ix->device));
+    const lm_status rc = guarded(ix, "lm_index_screen_genomes: the host could not hold the batch or its rows", [&]() {
         const HostIndex &h = ix->host;
         const double t0 = now_ms();
-        if (opt.windows < 1) throw ScreenArg("lm_index_screen_genomes: windows = " + std::to_string(opt.windows) + ", needs to be > 0");
-        if (opt.top_n < 0) throw ScreenArg("lm_index_screen_genomes: top_n = " + std::to_string(opt.top_n) + " is negative");
+        if (opt.windows < 1) throw ArgError("lm_index_screen_genomes: windows = " + std::to_string(opt.windows) + ", needs to be > 0");
+        if (opt.top_n < 0) throw ArgError("lm_index_screen_genomes: top_n = " + std::to_string(opt.top_n) + " is negative");
         if (opt.min_prefix > h.k || opt.min_prefix < h.mask_prefix + h.anchor_prefix)
-            throw ScreenOption("lm_index_screen_genomes: min_prefix (" + std::to_string(opt.min_prefix) + ") should be in the range of [" +
+            throw OptionError("lm_index_screen_genomes: min_prefix (" + std::to_string(opt.min_prefix) + ") should be in the range of [" +
                                std::to_string(h.mask_prefix + h.anchor_prefix) + ", " + std::to_string(h.k) + "]");
-        if (nq > 0 && !queries) throw ScreenArg("lm_index_screen_genomes: queries is NULL but nq is not 0");
-        if (nq >= ((size_t)1 << 31)) throw ScreenArg("lm_index_screen_genomes: more than 2^31 queries");
+        if (nq > 0 && !queries) throw ArgError("lm_index_screen_genomes: queries is NULL but nq is not 0");
+        if (nq >= ((size_t)1 << 31)) throw ArgError("lm_index_screen_genomes: more than 2^31 queries");
         std::vector<ScreenLayout> lay(nq);
         for (size_t q = 0; q < nq; q++) {
             const std::string name = "query " + std::to_string(q) + (queries[q].id ? std::string(" (") + queries[q].id + ")" : std::string());
-            if (queries[q].ncontigs == 0 || !queries[q].contigs) throw ScreenArg("lm_index_screen_genomes: " + name + " has no contigs");
+            if (queries[q].ncontigs == 0 || !queries[q].contigs) throw ArgError("lm_index_screen_genomes: " + name + " has no contigs");
             std::vector<uint32_t> cl(queries[q].ncontigs);
             for (size_t c = 0; c < cl.size(); c++) {
                 cl[c] = queries[q].contigs[c].len;
-                if (cl[c] && !queries[q].contigs[c].seq) throw ScreenArg("lm_index_screen_genomes: contig " + std::to_string(c) + " of " + name + " has no sequence");
+                if (cl[c] && !queries[q].contigs[c].seq) throw ArgError("lm_index_screen_genomes: contig " + std::to_string(c) + " of " + name + " has no sequence");
             }
             screen_layout(cl.data(), cl.size(), h.k, lay[q]);
             if (lay[q].len >= ((int64_t)1 << 28))
-                throw ScreenArg("lm_index_screen_genomes: " + name + " has " + std::to_string((long long)lay[q].len) +
+                throw ArgError("lm_index_screen_genomes: " + name + " has " + std::to_string((long long)lay[q].len) +
                                 " bases with its spacers; a query genome must stay below 2^28");
         }
         // sub-batches: window records x masks stay below 2^30 lookup slots, the concatenations below 2^30 bytes
@@ -576,7 +560,7 @@ extern "C" lm_status lm_index_screen_genomes(lm_index *ix, const lm_genome_query
                 bases += b;
                 q1++;
             }
-            if (slots >= ((int64_t)1 << 32)) throw ScreenArg("lm_index_screen_genomes: windows x masks of one query must stay below 2^32");
+            if (slots >= ((int64_t)1 << 32)) throw ArgError("lm_index_screen_genomes: windows x masks of one query must stay below 2^32");
             screen_sub_batch(ix, queries, lay, q0, q1, opt, so);
             q0 = q1;
         }
@@ -594,13 +578,10 @@ extern "C" lm_status lm_index_screen_genomes(lm_index *ix, const lm_genome_query
         }
         std::vector<ScreenRow> rows;
         screen_rows(hits, opt.top_n, rows);
-        std::vector<lm_hsp> names(rows.size());
-        for (size_t i = 0; i < rows.size(); i++) {
-            memset(&names[i], 0, sizeof(lm_hsp));
-            names[i].batch_genome = rows[i].keys[0];
-            names[i].seq_idx = -1;
-        }
-        lm_attach_names(ix, names.data(), names.size());
+        std::vector<uint64_t> first_key(rows.size());
+        for (size_t i = 0; i < rows.size(); i++) first_key[i] = rows[i].keys[0];
+        std::vector<const char *> names;
+        genome_ids_of_keys(ix, first_key, names);
         for (size_t i = 0; i < rows.size(); i++) {
             const ScreenRow &r = rows[i];
             const ScreenPartial &d = recs[r.detail];
@@ -610,7 +591,7 @@ extern "C" lm_status lm_index_screen_genomes(lm_index *ix, const lm_genome_query
             o.nkeys = (uint32_t)r.keys.size();
             o.score = r.score;
             o.batch_genome = r.keys[0];
-            o.genome_id = names[i].genome_id;
+            o.genome_id = names[i];
             o.keys_off = res->keys.size();
             res->keys.insert(res->keys.end(), r.keys.begin(), r.keys.end());
             o.prefixes_off = res->prefixes.size();
@@ -629,25 +610,9 @@ extern "C" lm_status lm_index_screen_genomes(lm_index *ix, const lm_genome_query
         }
         res->stats = so.stats;
         res->stats.ms_total = now_ms() - t0;
-    } catch (const lm::ScreenArg &e) {
-        ix->err = e.what();
-        return LM_ERR_ARG;
-    } catch (const lm::ScreenOption &e) {
-        ix->err = e.what();
-        return LM_ERR_OPTION;
-    } catch (const DeviceOOM &e) {
-        (void)hipGetLastError();
-        ix->err = e.what();
-        return LM_ERR_NOMEM;
-    } catch (const std::bad_alloc &) {
-        ix->err = "lm_index_screen_genomes: the host could not hold the batch or its rows";
-        return LM_ERR_NOMEM;
-    } catch (const std::exception &e) {
-        ix->err = e.what();
-        return LM_ERR_HIP;
-    }
-    *out = res.release();
-    return LM_OK;
+    });
+    if (rc == LM_OK) *out = res.release();
+    return rc;
 }
 
 
@@ -664,11 +629,11 @@ static void screen_local_structure(lm_index *ix, std::vector<uint64_t> &bits, st
     const hipStream_t st = ix->lane[0].main.st;
     const DevIndexView &v = ix->view;
     W = (v.P1 - 1 + 63) / 64;
-    if (W > 64) throw ScreenArg("screen structure: a partition index of more than 6 bases is not supported");
+    if (W > 64) throw ArgError("screen structure: a partition index of more than 6 bases is not supported");
     const size_t nb = (size_t)2 * v.M * W;
     DBuf<uint64_t> d;
     d.alloc_exact(nb);
-    hipLaunchKernelGGL(k_screen_occupancy, dim3(sc_grid((int64_t)nb)), dim3(256), 0, st, v, W, d.p);
+    hipLaunchKernelGGL(k_screen_occupancy, dim3(grid_for((int64_t)nb)), dim3(256), 0, st, v, W, d.p);
     HIPCHK(hipGetLastError());
     bits.resize(nb);
     off.resize((size_t)2 * v.M + 1);
@@ -681,34 +646,14 @@ static void screen_local_structure(lm_index *ix, std::vector<uint64_t> &bits, st
 }
 } // namespace lm
 
-template <typename Body> static lm_status screen_call(lm_index *ix, Body body) {
-    std::lock_guard<std::mutex> lock(ix->mu);
-    try {
-        HIPCHK(hipSetDevice(ix->device));
-        body();
-        return LM_OK;
-    } catch (const lm::ScreenArg &e) {
-        ix->err = e.what();
-        return LM_ERR_ARG;
-    } catch (const DeviceOOM &e) {
-        (void)hipGetLastError();
-        ix->err = e.what();
-        return LM_ERR_NOMEM;
-    } catch (const std::bad_alloc &) {
-        ix->err = "screen structure: the host could not hold it";
-        return LM_ERR_NOMEM;
-    } catch (const std::exception &e) {
-        ix->err = e.what();
-        return LM_ERR_HIP;
-    }
-}
+static const char *const SC_STRUCTURE_NOMEM = "screen structure: the host could not hold it"; // (neither call throws an OptionError)
 
 extern "C" lm_status lm_index_screen_structure(lm_index *ix, void **blob, size_t *bytes) {
     using namespace lm;
     if (!ix || !blob || !bytes) return LM_ERR_ARG;
     *blob = nullptr;
     *bytes = 0;
-    return screen_call(ix, [&]() {
+    return guarded(ix, SC_STRUCTURE_NOMEM, [&]() {
         std::vector<uint64_t> bits, kmers;
         std::vector<int64_t> off;
         int W = 0;
@@ -730,7 +675,7 @@ extern "C" lm_status lm_index_screen_structure(lm_index *ix, void **blob, size_t
 extern "C" lm_status lm_index_screen_add_structure(lm_index *ix, const void *blob, size_t bytes) {
     using namespace lm;
     if (!ix) return LM_ERR_ARG;
-    return screen_call(ix, [&]() {
+    return guarded(ix, SC_STRUCTURE_NOMEM, [&]() {
         if (!blob || bytes == 0) { // back to the handle's own lists
             ix->sc_set = false;
             return;
@@ -738,16 +683,16 @@ extern "C" lm_status lm_index_screen_add_structure(lm_index *ix, const void *blo
         const hipStream_t st = ix->lane[0].main.st;
         const HostIndex &h = ix->host;
         ScreenBlobHead hd;
-        if (bytes < sizeof hd) throw ScreenArg("lm_index_screen_add_structure: the blob is shorter than its header");
+        if (bytes < sizeof hd) throw ArgError("lm_index_screen_add_structure: the blob is shorter than its header");
         memcpy(&hd, blob, sizeof hd);
         const int Wl = (ix->view.P1 - 1 + 63) / 64;
-        if (hd.magic != SC_BLOB_MAGIC) throw ScreenArg("lm_index_screen_add_structure: not a structure of lm_index_screen_structure");
+        if (hd.magic != SC_BLOB_MAGIC) throw ArgError("lm_index_screen_add_structure: not a structure of lm_index_screen_structure");
         if (hd.K != h.k || hd.M != h.M || hd.p != h.mask_prefix || hd.a != ix->view.part_bases || hd.W != Wl)
-            throw ScreenArg("lm_index_screen_add_structure: the structure is of an index with other k, masks or partitions (k " + std::to_string(hd.K) +
+            throw ArgError("lm_index_screen_add_structure: the structure is of an index with other k, masks or partitions (k " + std::to_string(hd.K) +
                             ", " + std::to_string(hd.M) + " masks, " + std::to_string(hd.a) + " partition bases)");
         const size_t nb = (size_t)2 * h.M * Wl, no = (size_t)2 * h.M + 1;
         if (hd.nout < 0 || bytes != sizeof hd + nb * 8 + no * 8 + (size_t)hd.nout * 8)
-            throw ScreenArg("lm_index_screen_add_structure: the blob's length does not fit its header");
+            throw ArgError("lm_index_screen_add_structure: the blob's length does not fit its header");
         // (a caller's buffer need not be aligned: the three arrays are copied out)
         std::vector<uint64_t> fb(nb), fk((size_t)hd.nout);
         std::vector<int64_t> fo(no);
@@ -755,11 +700,11 @@ extern "C" lm_status lm_index_screen_add_structure(lm_index *ix, const void *blo
         memcpy(fb.data(), src, nb * 8);
         memcpy(fo.data(), src + nb * 8, no * 8);
         if (hd.nout) memcpy(fk.data(), src + nb * 8 + no * 8, (size_t)hd.nout * 8);
-        if (fo[0] != 0 || fo[no - 1] != hd.nout) throw ScreenArg("lm_index_screen_add_structure: the blob's outlier table is broken");
+        if (fo[0] != 0 || fo[no - 1] != hd.nout) throw ArgError("lm_index_screen_add_structure: the blob's outlier table is broken");
         for (size_t i = 0; i + 1 < no; i++) {
-            if (fo[i + 1] < fo[i]) throw ScreenArg("lm_index_screen_add_structure: the blob's outlier table is broken");
+            if (fo[i + 1] < fo[i]) throw ArgError("lm_index_screen_add_structure: the blob's outlier table is broken");
             if (!std::is_sorted(fk.begin() + fo[i], fk.begin() + fo[i + 1]))
-                throw ScreenArg("lm_index_screen_add_structure: the outlier k-mers of list " + std::to_string(i) + " of the blob are not ascending");
+                throw ArgError("lm_index_screen_add_structure: the outlier k-mers of list " + std::to_string(i) + " of the blob are not ascending");
         }
         // the union is made beside what the handle holds and takes its place only when it is whole, on the host and on the
         // device; a failure on the way leaves the handle with its own lists (sc_set = false), never with half of a union

@@ -435,12 +435,6 @@ static SpParams sp_params(const SeedPacker &sp) {
     return p;
 }
 
-static int bits_for(int64_t n) { // bits needed for values in [0, n)
-    int b = 1;
-    while (((int64_t)1 << b) < n) b++;
-    return b;
-}
-
 void SeedPacker::begin(lm_index *ix_, int64_t local_genomes, int64_t max_genome_len) {
     ix = ix_;
     const HostIndex &h = ix->host;
@@ -660,10 +654,6 @@ extern "C" lm_status lm_index_mask_seeds(lm_index *ix, int32_t mask, uint64_t *k
 // cuts them into the per-record lists, k_sd_pass applies the distance rule of lm_seed_dist.h.
 namespace lm {
 
-struct SeedArg : std::runtime_error { // a refused argument: LM_ERR_ARG, the handle stays usable
-    explicit SeedArg(const std::string &m) : std::runtime_error(m) {}
-};
-
 // which records are wanted: main seeds carry a local record number, outliers the record's key
 struct SeedSelDev {
     const int32_t *slot_of_local; // [nlocal] slot in the selection, -1: not selected
@@ -863,8 +853,8 @@ static void seed_lists(lm_index *ix, const char *who, const uint64_t *keys, size
     const int64_t nlocal = (int64_t)h.genomes.size();
     const int M = h.M;
     const bool dbg = getenv("LM_DEBUG") != nullptr;
-    if (!keys && nkeys > 0) throw SeedArg(std::string(who) + ": keys is NULL but nkeys is not 0");
-    if (nkeys >= ((size_t)1 << 31)) throw SeedArg(std::string(who) + ": more than 2^31 keys");
+    if (!keys && nkeys > 0) throw ArgError(std::string(who) + ": keys is NULL but nkeys is not 0");
+    if (nkeys >= ((size_t)1 << 31)) throw ArgError(std::string(who) + ": more than 2^31 keys");
     // ---- the selection
     const bool all = keys == nullptr;
     std::vector<int32_t> slot_of_local((size_t)nlocal, -1);
@@ -881,11 +871,11 @@ static void seed_lists(lm_index *ix, const char *who, const uint64_t *keys, size
             const std::string name = "key " + std::to_string(keys[s]) + " (batch " + std::to_string(keys[s] >> 17) + ", index " + std::to_string(keys[s] & 0x1ffff) + ")";
             if (it == local_of.end()) {
                 if (h.other_of.count(keys[s]))
-                    throw SeedArg(std::string(who) + ": " + name + " is a record of another shard (this handle is shard " + std::to_string(h.shard_rank) +
+                    throw ArgError(std::string(who) + ": " + name + " is a record of another shard (this handle is shard " + std::to_string(h.shard_rank) +
                                   " of " + std::to_string(h.shard_count) + " and answers for its own records)");
-                throw SeedArg(std::string(who) + ": " + name + " is no record of this index");
+                throw ArgError(std::string(who) + ": " + name + " is no record of this index");
             }
-            if (slot_of_local[(size_t)it->second] >= 0) throw SeedArg(std::string(who) + ": " + name + " is given twice");
+            if (slot_of_local[(size_t)it->second] >= 0) throw ArgError(std::string(who) + ": " + name + " is given twice");
             slot_of_local[(size_t)it->second] = (int32_t)s;
             L.keys.push_back(keys[s]);
             L.local.push_back((int64_t)it->second);
@@ -1007,35 +997,14 @@ struct lm_seed_dist {
     std::vector<lm_seed_dist_row> rows;
 };
 
-// runs `body` under the index lock; refusals and failures become a status and a text on the handle
-template <typename Body> static lm_status seed_call(lm_index *ix, Body body) {
-    std::lock_guard<std::mutex> lock(ix->mu);
-    try {
-        HIPCHK(hipSetDevice(ix->device));
-        body();
-        return LM_OK;
-    } catch (const lm::SeedArg &e) {
-        ix->err = e.what();
-        return LM_ERR_ARG;
-    } catch (const DeviceOOM &e) {
-        (void)hipGetLastError();
-        ix->err = e.what();
-        return LM_ERR_NOMEM;
-    } catch (const std::bad_alloc &) {
-        ix->err = "seed positions: the host could not hold the result";
-        return LM_ERR_NOMEM;
-    } catch (const std::exception &e) {
-        ix->err = e.what();
-        return LM_ERR_HIP;
-    }
-}
+static const char *const SEED_NOMEM = "seed positions: the host could not hold the result"; // (both calls: lm::guarded)
 
 extern "C" lm_status lm_index_seed_positions(lm_index *ix, const uint64_t *keys, size_t nkeys, lm_seedpos **out) {
     if (!ix || !out) return LM_ERR_ARG;
     *out = nullptr;
     std::unique_ptr<lm_seedpos> res(new lm_seedpos());
     const hipStream_t stream = ix->lane[0].main.st;
-    const lm_status st = seed_call(ix, [&]() {
+    const lm_status st = guarded(ix, SEED_NOMEM, [&]() {
         lm::SeedLists L;
         lm::seed_lists(ix, "lm_index_seed_positions", keys, nkeys, L);
         res->keys = L.keys;
@@ -1065,9 +1034,9 @@ extern "C" lm_status lm_index_seed_distances(lm_index *ix, const uint64_t *keys,
     if (opt_in) opt = *opt_in;
     std::unique_ptr<lm_seed_dist> res(new lm_seed_dist());
     const hipStream_t stream = ix->lane[0].main.st;
-    const lm_status st = seed_call(ix, [&]() {
-        if (opt.hist_bins > 0 && opt.hist_width < 1) throw SeedArg("lm_index_seed_distances: hist_bins = " + std::to_string(opt.hist_bins) + " with hist_width < 1");
-        if (opt.hist_bins > 4096) throw SeedArg("lm_index_seed_distances: hist_bins = " + std::to_string(opt.hist_bins) + " (at most 4096 counters)");
+    const lm_status st = guarded(ix, SEED_NOMEM, [&]() {
+        if (opt.hist_bins > 0 && opt.hist_width < 1) throw ArgError("lm_index_seed_distances: hist_bins = " + std::to_string(opt.hist_bins) + " with hist_width < 1");
+        if (opt.hist_bins > 4096) throw ArgError("lm_index_seed_distances: hist_bins = " + std::to_string(opt.hist_bins) + " (at most 4096 counters)");
         SeedLists L;
         seed_lists(ix, "lm_index_seed_distances", keys, nkeys, L);
         const HostIndex &h = ix->host;

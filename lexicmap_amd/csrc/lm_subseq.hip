@@ -32,10 +32,6 @@
 
 namespace lm {
 
-struct SsArg : std::runtime_error {
-    explicit SsArg(const std::string &m) : std::runtime_error(m) {}
-};
-
 // `len` bases from base `start` of the 2-bit genome at src (device store or pinned host memory); top bit of len_rc: '-' strand.
 // The plan refuses a region that does not fit these fields (LM_SS_MAX_START, LM_SS_MAX_LEN in lm_subseq_plan.h).
 struct SsDevRegion {
@@ -72,6 +68,7 @@ __global__ __launch_bounds__(256) void k_subseq_extract(SsKernArgs a) {
     }
 }
 
+// (not the pipeline's parallel_for: the thread cap and the chunking differ, and with them the host's timing)
 template <typename F> static void ss_parallel_for(int64_t n, int64_t grain, F f) {
     if (n <= 0) return;
     const int nt = (int)std::min<int64_t>((n + grain - 1) / grain, std::min(16u, std::max(1u, std::thread::hardware_concurrency())));
@@ -210,7 +207,7 @@ template <typename Get> static void subseq_run(lm_index *ix, const char *who, si
     std::string refusal;
     if (!ss_plan(look, h.contig_interval, who, n, region, opt.upstream, opt.downstream, opt.ignore_errors != 0, items, refusal,
                  [](int64_t m, auto f) { ss_parallel_for(m, 1 << 16, f); }))
-        throw SsArg(refusal);
+        throw ArgError(refusal);
     std::vector<int64_t> lens(n), goff(n + 1);
     for (size_t i = 0; i < n; i++) lens[i] = items[i].status == SS_OK ? items[i].w.len : 0;
     const int64_t groups = ss_layout(lens.data(), n, goff.data());
@@ -349,26 +346,9 @@ template <typename Get> static lm_status subseq_call(lm_index *ix, const char *w
     std::unique_ptr<lm_subseqs> res(new lm_subseqs());
     memset(&res->stats, 0, sizeof res->stats);
     res->genome_seqs = genome_seqs;
-    std::lock_guard<std::mutex> lock(ix->mu);
-    try {
-        HIPCHK(hipSetDevice(ix->device));
-        subseq_run(ix, who, n, get, opt, *res);
-    } catch (const SsArg &e) {
-        ix->err = e.what();
-        return LM_ERR_ARG;
-    } catch (const DeviceOOM &e) {
-        (void)hipGetLastError();
-        ix->err = e.what();
-        return LM_ERR_NOMEM;
-    } catch (const std::bad_alloc &) {
-        ix->err = std::string(who) + ": the host could not hold the plan of the regions";
-        return LM_ERR_NOMEM;
-    } catch (const std::exception &e) {
-        ix->err = e.what();
-        return LM_ERR_HIP;
-    }
-    *out = res.release();
-    return LM_OK;
+    const lm_status rc = guarded(ix, who, ": the host could not hold the plan of the regions", [&]() { subseq_run(ix, who, n, get, opt, *res); });
+    if (rc == LM_OK) *out = res.release();
+    return rc;
 }
 
 } // namespace lm
